@@ -44,7 +44,14 @@ stream -- independent camera streams, no data-path collective ("scaling": "weak"
 o's GPU work runs on rank o.id % N and the result records are all-gathered over RCCL
 ("scaling": "strong").
 
-cpu_baseline: the CPU restatement under oracle/ (kind "port") rebuilt here with
+A plain run (`--gpus 1 --steps N --warmup W`) sets up, warms up, times the N steps and prints
+the result line: the headline figure and what the timed steps themselves recorded. Everything
+that takes runs of its own -- the CPU baseline and its parity block, the rooflines, the
+searches / pose / bag-of-words legs beside the step, the per-frame drop-in and chained legs --
+runs only with `--full`. `--dump-outputs DIR` writes what the last timed step computed as
+DIR/<name>.npy (dump_outputs), so that two builds can be compared output for output.
+
+cpu_baseline (--full): the CPU restatement under oracle/ (kind "port") rebuilt here with
 -O3 -march=native, timed on rank 0 on a bounded sample: (a) the reference's shape, one
 thread for extraction + matching + association; (b) all cores: extraction and matching
 frame-parallel over std::threads, the association (one decision chain) on one thread
@@ -224,6 +231,11 @@ def main():
                     help="extract+match single-thread CPU sample (60 frames; 3 at 1080p for config b)")
     ap.add_argument("--cpu-mt-frames", type=int, default=256, help="extract+match all-cores CPU sample")
     ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also everything beside the headline figure: CPU baseline and parity, rooflines, the "
+                         "searches / pose / bag-of-words legs, the per-frame drop-in and chained legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64)")
     ap.add_argument("--thread", action="store_true",
                     help="A/B: replay the association on a second thread while the frame work is enqueued")
     ap.add_argument("--shard", action="store_true",
@@ -235,7 +247,7 @@ def main():
                          "the association's launches; default: 24 for the Full stream (its frame work overlaps more "
                          "of the replay: +2 %%, profiles/r06_ab_full_frame_cus.txt), all for the others")
     ap.add_argument("--cu-layout", choices=["interleaved", "linear"], default="interleaved",
-                    help="A/B: CU-mask bit order (interleaved: bit i = CU i / 8 of XCD i % 8)")
+                    help="A/B: CU-mask bit order (interleaved: bit i = CU i / 8 of XCD i %% 8)")
     ap.add_argument("--no-dropin", action="store_true", help="skip the per-frame drop-in leg (dropin_leg)")
     ap.add_argument("--dropin-frames", type=int, default=405, help="frames of the per-frame drop-in leg")
     ap.add_argument("--chain-frames", type=int, default=120,
@@ -466,16 +478,20 @@ def main():
     ms_per_step = 1000.0 * elapsed / args.steps
     stage = np.mean(np.stack(rec["stage_ms"]), 0)
     match_ms = float(np.mean(rec["match_ms"]))
-    searches = search_legs(ea, torch, matcher, cam, stream, F, cap, poses, kps, cnt, mpos, has, sc, d_kps, d_desc,
-                           d_cnt, d_has, d_mpos, match_ms)
-    hl = d_lcnt.cpu().numpy()
-    lines_leg = {"in_step": True, "frames": F, "ms_per_step": lines_ms, "frames_per_s": F / (lines_ms * 1e-3),
-                 "mean_lines": float(hl.mean()), "kernels": "k_line_maps<3> (COLOR_BGR2GRAY, blur, Sobel, code, move words, "
-                 "anchor masks) + k_line_anchors + k_edge_lines (EdgeDrawing walk + EDline)",
-                 "input": "the step's 3-channel colour frames (rawImage of the EAO Frame ctor, Frame.cc:324)"}
-    pose = pose_leg(ea, torch, stream, F, cap, gpu, with_cpu=rank == 0 and not args.no_cpu_baseline)
-    bow = bow_leg(ea, torch, stream, F, cap, gpu, d_kps, d_desc, d_cnt, kps, cnt,
-                  with_cpu=rank == 0 and not args.no_cpu_baseline)
+    if args.dump_outputs and rank == 0 and args.steps > 0:
+        dump_outputs(args.dump_outputs, F, cap, d_frames, d_kps, d_desc, d_cnt, d_match, d_nm, d_lines, d_lcnt, out)
+    if args.full:
+        searches = search_legs(ea, torch, matcher, cam, stream, F, cap, poses, kps, cnt, mpos, has, sc, d_kps,
+                               d_desc, d_cnt, d_has, d_mpos, match_ms)
+        hl = d_lcnt.cpu().numpy()
+        lines_leg = {"in_step": True, "frames": F, "ms_per_step": lines_ms, "frames_per_s": F / (lines_ms * 1e-3),
+                     "mean_lines": float(hl.mean()),
+                     "kernels": "k_line_maps<3> (COLOR_BGR2GRAY, blur, Sobel, code, move words, "
+                                "anchor masks) + k_line_anchors + k_edge_lines (EdgeDrawing walk + EDline)",
+                     "input": "the step's 3-channel colour frames (rawImage of the EAO Frame ctor, Frame.cc:324)"}
+        pose = pose_leg(ea, torch, stream, F, cap, gpu, with_cpu=rank == 0 and not args.no_cpu_baseline)
+        bow = bow_leg(ea, torch, stream, F, cap, gpu, d_kps, d_desc, d_cnt, kps, cnt,
+                      with_cpu=rank == 0 and not args.no_cpu_baseline)
     n_kps = float(d_cnt.float().mean().item())
     ab = algorithmic_bytes(n_kps)
     dom = int(np.argmax(stage))
@@ -512,11 +528,26 @@ def main():
                        "frames_per_step": F, "features": NFEAT, "levels": NLEV, "assoc_flag": cfg["flag"],
                        "parallelism": "streams%d" % world,
                        "frame_work_cus_per_xcd": args.frame_cus or "all"},
+            "stages_ms_per_step": {n: float(v) for n, v in zip(STAGES, stage)},
+            # host time of the step's parts (ms): enqueueing the frame work, tearing down the last
+            # replay and creating this one, eao_replay_run
+            "step_split_ms": dict(zip(("front_enqueue", "replay_setup", "replay_run"),
+                                      (float(v) * 1e3 for v in np.mean(np.array(rec["split"]), 0)))),
+            "extract_ms_per_step": ext_ms,
+            "match_ms_per_step": match_ms,
+            "gray_ms_per_step": gray_ms,
+            "lines_ms_per_step": lines_ms,
+            "mean_keypoints": n_kps,
+            "mean_matches": float(d_nm[1:].float().mean().item()),
+            "assoc_detections": int(nb.sum()),
+        }
+    if rank == 0 and args.full:
+        # figures beside the headline: rooflines of the step's kernels and the legs timed in runs of their own
+        result.update({
             "roofline": {"bound": "hbm", "kernel": KERNELS[dom_name], "achieved": ach, "peak": PEAK_HBM_GBS,
                          "unit": "GB/s", "frac": ach / PEAK_HBM_GBS, "traffic": traffic,
                          "traffic_source": traffic_src,
                          "algorithmic_bytes_per_launch": dom_bytes * F, "avg_launch_ms": float(stage[dom])},
-            "stages_ms_per_step": {n: float(v) for n, v in zip(STAGES, stage)},
             # the pyramid's own line (HBM-bound: every level read once and written once; its launches
             # are timed together, so no per-launch traffic here -- the per-level PMC passes are in
             # profiles/r05_pmc_fetch.txt / r05_pmc_write.txt)
@@ -525,15 +556,9 @@ def main():
                                  "peak": PEAK_HBM_GBS, "unit": "GB/s",
                                  "frac": ab["pyramid"] * F / (float(stage[0]) * 1e-3) / 1e9 / PEAK_HBM_GBS,
                                  "algorithmic_bytes_per_step": ab["pyramid"] * F, "ms_per_step": float(stage[0])},
-            # host time of the step's parts (ms): enqueueing the frame work, tearing down the last
-            # replay and creating this one, eao_replay_run
-            "step_split_ms": dict(zip(("front_enqueue", "replay_setup", "replay_run"),
-                                      (float(v) * 1e3 for v in np.mean(np.array(rec["split"]), 0)))),
             "roofline_valu": valu_roof(KERNELS[dom_name], F, float(stage[dom])),
-            "extract_ms_per_step": ext_ms,
             "extract_fps": F / (ext_ms * 1e-3),
             "extract_gbs": ab["extract"] * F / (ext_ms * 1e-3) / 1e9,
-            "match_ms_per_step": match_ms,
             "searches": searches,
             "line_detect": lines_leg,
             "pose_optimization": pose,
@@ -542,23 +567,21 @@ def main():
                                   "frames": F, "ms": gray_ms, "achieved_gbs": gray_bytes / (gray_ms * 1e-3) / 1e9,
                                   "frac_hbm_peak": gray_bytes / (gray_ms * 1e-3) / 1e9 / PEAK_HBM_GBS,
                                   "note": "a stage of the step: colour frames in HBM -> mImGray for the extraction"},
-            "mean_keypoints": n_kps,
-            "mean_matches": float(d_nm[1:].float().mean().item()),
-            "assoc_detections": int(nb.sum()),
-        }
+        })
+    if rank == 0:
         prof = np.zeros(24)
         ea.lib().eao_replay_profile(out["replay"].h, ea.P(prof))
         result["assoc_profile_us_per_frame"] = {
             "frame": prof[0] / F, "local_mapping": prof[1] / F, "forest_wait": prof[3] / F,
             "frame_start": prof[14] / F, "assoc_loop": prof[15] / F, "forest_launches_per_frame": prof[2] / F}
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         result["cpu_baseline"], result["parity"] = cpu_baseline(args, cfg, assoc_frames, d_frames, poses, kps, cnt,
                                                                 mpos, has, sc, d_desc, d_match, d_nm, out,
                                                                 d_color, d_lines, d_lcnt)
         result["gpu_over_cpu"] = {"all_cores": result["value"] / result["cpu_baseline"]["value"],
                                   "single_thread": result["value"] / result["cpu_baseline"]["single_thread"]["value"]}
-    if rank == 0 and world == 1 and not args.no_dropin:
+    if rank == 0 and world == 1 and args.full and not args.no_dropin:
         # the per-frame legs stand for a process that uses the single-frame entry points only: the
         # step's engines (their streams, HSA queues and buffers) are released first, so the legs do
         # not share the device's hardware queues with idle ones
@@ -570,7 +593,7 @@ def main():
         result["dropin_per_frame"] = dropin_leg(ea, gpu, assoc_frames[:kd], d_color[:kd].cpu().numpy(),
                                                 d_frames[:kd].cpu().numpy(), poses[:kd], cfg["flag"],
                                                 check=not args.no_cpu_baseline)
-    if rank == 0 and world == 1 and not args.no_dropin and args.chain_frames > 0:
+    if rank == 0 and world == 1 and args.full and not args.no_dropin and args.chain_frames > 0:
         result["chained_per_frame"] = chained_leg(ea, args.chain_frames, check=not args.no_cpu_baseline)
     if world > 1:
         dist.barrier()
@@ -578,6 +601,60 @@ def main():
     if rank == 0:
         print(json.dumps(result, default=float), flush=True)
     return 0
+
+
+DUMP_FRAMES = 64  # frames of the per-frame arrays kept by --dump-outputs (a fixed seeded sample)
+DUMP_GRAY = 8     # of these, the frames whose grey image is kept
+
+
+def dump_outputs(path, F, cap, d_frames, d_kps, d_desc, d_cnt, d_match, d_nm, d_lines, d_lcnt, out):
+    """--dump-outputs: what the last timed step handed its caller, as <path>/<name>.npy in
+    float32 / float64 (every value is an integer or a float32, so the casts are exact). The
+    per-frame counts, the association's decisions and the object map are whole; keypoints,
+    descriptors, match ids, line segments and grey frames are kept for a fixed seeded sample
+    of frames (sample_frames.npy), rows past a frame's count zeroed -- 21 MB for the 405-frame stream."""
+    import eao_accel as ea
+    rng = np.random.default_rng(0xD0)
+    sel = np.sort(rng.choice(F, min(F, DUMP_FRAMES), replace=False))
+    gsel = sel[:DUMP_GRAY]
+    cnt, nm, lcnt = (x.cpu().numpy() for x in (d_cnt, d_nm, d_lcnt))
+
+    def rows(t, idx, n):  # the sampled frames of a device array on the host, rows past the count zeroed
+        a = t[idx.tolist()].cpu().numpy()
+        for i, k in enumerate(n[idx]):
+            a[i, min(int(k), a.shape[1]):] = 0
+        return a
+    kp = rows(d_kps, sel, cnt).view(ea.KP_DTYPE).reshape(len(sel), cap)
+    arrays = {
+        "sample_frames": sel.astype(np.float64),
+        "keypoint_count": cnt.astype(np.float64),
+        "match_count": nm.astype(np.float64),
+        "line_count": lcnt.astype(np.float64),
+        "keypoints": np.stack([kp[n].astype(np.float32) for n in ea.KP_DTYPE.names], -1),
+        "descriptors": rows(d_desc, sel, cnt).astype(np.float32),
+        "matches": rows(d_match, sel, cnt).astype(np.float32),
+        "lines": rows(d_lines, sel, lcnt).astype(np.float32),
+        "gray": d_frames[gsel.tolist()].cpu().numpy().astype(np.float32),
+    }
+    arrays.update(assoc_arrays(out["det"], out["replay"]))
+    save_arrays(path, arrays)
+
+
+def assoc_arrays(det, replay):
+    """The association's outputs for --dump-outputs: its per-box decisions and the object map it
+    leaves (a NaN statistic is stored as 0 and flagged in object_float_isnan, so that equal maps
+    compare equal)."""
+    oi, of, _ = replay.objects()
+    return {"assoc_detections": det.astype(np.float64), "object_ints": oi.astype(np.float64),
+            "object_floats": np.where(np.isnan(of), np.float32(0), of).astype(np.float32),
+            "object_float_isnan": np.isnan(of).astype(np.float32)}
+
+
+def save_arrays(path, arrays):
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64)
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def chained_leg(ea, n, check=True):
@@ -1261,7 +1338,9 @@ def run_config_c(args, rank, world, gpu):
             "replay_profile_us_per_frame": {"iforest_wait": prof[3] / nfr, "np": prof[5] / nfr,
                                             "frame_start": prof[7] / nfr},
         }
-        if not args.no_cpu_baseline and args.cpu_frames > 0:
+        if args.dump_outputs and args.steps > 0:
+            save_arrays(args.dump_outputs, assoc_arrays(det, rp))
+        if args.full and not args.no_cpu_baseline and args.cpu_frames > 0:
             sys.path.insert(0, os.path.join(ROOT, "oracle"))
             import pyoracle as orc  # checker / CPU baseline only
             orc.use_native()

@@ -65,6 +65,25 @@ def algorithmic_bytes(n_kps):
             "describe": l0 + upper + n_kps * 60, "extract": l0 + 2 * upper + n_kps * 60}
 
 
+def dump_outputs(path, F, cap, d_kps, d_cnt, d_match, d_nm, keep=16):
+    """--dump-outputs: the last timed step's per-frame counts, and the keypoints and match ids of
+    a fixed seeded sample of frames (rows past a frame's count zeroed), as float32 / float64 .npy."""
+    os.makedirs(path, exist_ok=True)
+    sel = np.sort(np.random.default_rng(0xD0).choice(F, min(F, keep), replace=False))
+    cnt = d_cnt.cpu().numpy()
+    kp, mt = d_kps[sel.tolist()].cpu().numpy(), d_match[sel.tolist()].cpu().numpy()
+    for i, k in enumerate(cnt[sel]):
+        kp[i, int(k):] = 0
+        mt[i, int(k):] = 0
+    kp = kp.view(ea.KP_DTYPE).reshape(len(sel), cap)
+    arrays = {"sample_frames": sel.astype(np.float64), "keypoint_count": cnt.astype(np.float64),
+              "match_count": d_nm.cpu().numpy().astype(np.float64),
+              "keypoints": np.stack([kp[n].astype(np.float32) for n in ea.KP_DTYPE.names], -1),
+              "matches": mt.astype(np.float32)}
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=256)
@@ -72,6 +91,10 @@ def parser():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--cpu-frames", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="also the per-stage pass with its roofline and the CPU baseline with its parity block")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's counts, keypoints and match ids as DIR/<name>.npy")
     return ap
 
 
@@ -166,19 +189,35 @@ def main(args=None):
     torch.cuda.synchronize(dev)
     eao_dist.barrier()
     elapsed = eao_dist.max_over_ranks(time.perf_counter() - t0, dev)
+    if args.dump_outputs and rank == 0 and args.steps > 0:
+        dump_outputs(args.dump_outputs, F, cap, d_kps, d_cnt, d_match, d_nm)
     # per-stage times in a separate pass (reading them back between steps
     # would put host syncs inside the timed region)
-    orb.set_timing(True)
     stages, mms = [], []
-    for _ in range(3):
-        step()
-        stream.synchronize()
-        stages.append(orb.stage_ms())
-        mms.append(ev_m0.elapsed_time(ev_m1))
-    orb.set_timing(False)
+    if args.full:
+        orb.set_timing(True)
+        for _ in range(3):
+            step()
+            stream.synchronize()
+            stages.append(orb.stage_ms())
+            mms.append(ev_m0.elapsed_time(ev_m1))
+        orb.set_timing(False)
 
     result = None
     if rank == 0:
+        result = {
+            "metric": "frames/sec (ORB extract+match) on 1920x1080, 4000 features, 8 levels",
+            "value": F * args.steps * world / elapsed, "unit": "frames/s", "n_gpus": world, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True,
+            "scaling": "weak", "vs_baseline": None, "dtype": "u8",
+            "data": "synthetic (procedural textured plane along a smooth camera path, seed 0xEA4; %d rendered "
+                    "frames repeated to %d; SURVEY §8d input 5)" % (U, F),
+            "config": {"workload": "Config B: synthetic 1920x1080 stream, %d frames/rank/step, 4000 features, "
+                                   "8 levels" % F, "frames_per_step": F, "parallelism": "frames%d" % world},
+            "mean_keypoints": float(d_cnt.float().mean().item()),
+            "mean_matches": float(d_nm[1:].float().mean().item()),
+        }
+    if rank == 0 and args.full:
         names = ["pyramid", "fast", "distribute", "describe"]  # blur fused into k_describe
         stage = np.mean(np.stack(stages), 0)
         n_kps = float(d_cnt.float().mean().item())
@@ -189,15 +228,7 @@ def main(args=None):
         ext_ms = float(stage.sum())
         kern = {"pyramid": "k_resize_tile (x7)", "fast": "k_fast_band", "distribute": "k_distribute",
                 "describe": "k_describe"}
-        result = {
-            "metric": "frames/sec (ORB extract+match) on 1920x1080, 4000 features, 8 levels",
-            "value": F * args.steps * world / elapsed, "unit": "frames/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": "u8",
-            "data": "synthetic (procedural textured plane along a smooth camera path, seed 0xEA4; %d rendered "
-                    "frames repeated to %d; SURVEY §8d input 5)" % (U, F),
-            "config": {"workload": "Config B: synthetic 1920x1080 stream, %d frames/rank/step, 4000 features, "
-                                   "8 levels" % F, "frames_per_step": F, "parallelism": "frames%d" % world},
+        result.update({
             "roofline": {"bound": "hbm", "kernel": kern[names[dom]], "achieved": ach, "peak": PEAK_HBM_GBS,
                          "unit": "GB/s", "frac": ach / PEAK_HBM_GBS, "traffic": None,
                          "algorithmic_bytes_per_launch": dom_bytes * F, "avg_launch_ms": float(stage[dom])},
@@ -205,8 +236,7 @@ def main(args=None):
             "extract_ms_per_step": ext_ms, "extract_fps": F / (ext_ms * 1e-3),
             "extract_gbs": ab["extract"] * F / (ext_ms * 1e-3) / 1e9,
             "match_ms_per_step": float(np.mean(mms)),
-            "mean_keypoints": n_kps, "mean_matches": float(d_nm[1:].float().mean().item()),
-        }
+        })
         if world == 1 and args.cpu_frames > 0:
             sys.path.insert(0, os.path.join(ROOT, "oracle"))
             import pyoracle as orc  # checker / CPU baseline only
