@@ -40,6 +40,15 @@ int orc_orb_pyramid(const uint8_t* img, int w, int h, float scale_factor, int nl
    vToDistributeKeys order (coordinates relative to minBorder like the reference) */
 int orc_orb_level_candidates(const uint8_t* level, int w, int h, int iniTh, int minTh,
                              orc_keypoint* out, int cap, int* n_out);
+/* per-stage entry points (the functions orc_orb_extract composes), for the comparison with
+   oracle/orb_py.py: DistributeOctTree on a candidate list (survivors' indices, result order);
+   IC_Angle's moments and angle at level positions; computeOrbDescriptor on a blurred level */
+int orc_orb_distribute(const orc_keypoint* cand, int n, int minX, int maxX, int minY, int maxY, int N,
+                       int* sel, int* n_sel);
+int orc_orb_orientation(const uint8_t* level, int w, int h, int n, const float* x, const float* y,
+                        int* m10, int* m01, float* angle);
+int orc_orb_describe(const uint8_t* blurred, int w, int h, int n, const float* x, const float* y,
+                     const float* angle, uint8_t* desc);
 /* 7x7 sigma=2 REFLECT_101 blur (8U fixed-point path) */
 int orc_gaussian_blur7(const uint8_t* src, int w, int h, uint8_t* dst);
 float orc_fast_atan2(float y, float x);

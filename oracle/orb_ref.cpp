@@ -492,8 +492,9 @@ float fast_atan2(float y, float x) {
 }
 
 // IC_Angle, ORBextractor.cc:77-104 (image = level, row stride = cols)
-static float ic_angle(const uint8_t* img, int stride, float px, float py, const int* umax) {
-  int m_01 = 0, m_10 = 0;
+static void ic_moments(const uint8_t* img, int stride, float px, float py, const int* umax, int& m_10,
+                       int& m_01) {
+  m_01 = 0, m_10 = 0;
   const uint8_t* center = img + (size_t)cvRound(py) * stride + cvRound(px);
   for (int u = -HALF_PATCH_SIZE; u <= HALF_PATCH_SIZE; ++u) m_10 += u * center[u];
   for (int v = 1; v <= HALF_PATCH_SIZE; ++v) {
@@ -506,6 +507,11 @@ static float ic_angle(const uint8_t* img, int stride, float px, float py, const 
     }
     m_01 += v * v_sum;
   }
+}
+
+static float ic_angle(const uint8_t* img, int stride, float px, float py, const int* umax) {
+  int m_01, m_10;
+  ic_moments(img, stride, px, py, umax, m_10, m_01);
   return fast_atan2((float)m_01, (float)m_10);
 }
 
@@ -658,6 +664,46 @@ int orc_orb_level_candidates(const uint8_t* level, int w, int h, int iniTh, int 
   *n_out = (int)c.size();
   if ((int)c.size() > cap) return -1;
   std::copy(c.begin(), c.end(), out);
+  return 0;
+}
+
+// Per-stage entry points for the stage-by-stage comparison with oracle/orb_py.py
+// (tests/test_oracle_orb_py.py): the same static functions orc_orb_extract composes.
+
+// DistributeOctTree on a given candidate list (x, y relative to the border corner):
+// the survivors' indices into cand, in result order.
+int orc_orb_distribute(const orc_keypoint* cand, int n, int minX, int maxX, int minY, int maxY, int N,
+                       int* sel, int* n_sel) {
+  std::vector<orc_keypoint> K(cand, cand + n);
+  std::vector<int> s = distribute_octtree(K, minX, maxX, minY, maxY, N);
+  *n_sel = (int)s.size();
+  std::copy(s.begin(), s.end(), sel);
+  return 0;
+}
+
+// IC_Angle at n level positions: the integer moments and the fastAtan2 angle.
+int orc_orb_orientation(const uint8_t* level, int w, int h, int n, const float* x, const float* y,
+                        int* m10, int* m01, float* angle) {
+  (void)h;
+  Params p = make_params(1000, 1.2f, 8, 20, 7);
+  for (int i = 0; i < n; i++) {
+    ic_moments(level, w, x[i], y[i], p.umax, m10[i], m01[i]);
+    angle[i] = ic_angle(level, w, x[i], y[i], p.umax);
+  }
+  return 0;
+}
+
+// computeOrbDescriptor at n level positions of an already blurred level.
+int orc_orb_describe(const uint8_t* blurred, int w, int h, int n, const float* x, const float* y,
+                     const float* angle, uint8_t* desc) {
+  (void)h;
+  for (int i = 0; i < n; i++) {
+    orc_keypoint kp{};
+    kp.x = x[i];
+    kp.y = y[i];
+    kp.angle = angle[i];
+    orb_descriptor(kp, blurred, w, desc + 32 * (size_t)i);
+  }
   return 0;
 }
 

@@ -97,6 +97,50 @@ def pyramid(img, scale=1.2, nlevels=8):
     return levels
 
 
+def level_candidates(level, ini=20, mn=7):
+    """Cell loop of ComputeKeyPointsOctTree on one level: the candidates (KP_DTYPE, x / y relative
+    to the border corner) in vToDistributeKeys order."""
+    level = np.ascontiguousarray(level, np.uint8)
+    h, w = level.shape
+    cap = w * h
+    out = np.zeros(cap, KP_DTYPE)
+    n = ctypes.c_int()
+    rc = lib().orc_orb_level_candidates(P(level), w, h, ini, mn, P(out), cap, ctypes.byref(n))
+    assert rc == 0, rc
+    return out[:n.value].copy()
+
+
+def distribute(cands, min_x, max_x, min_y, max_y, n_want):
+    """DistributeOctTree on a candidate list (KP_DTYPE): the survivors' indices in result order."""
+    cands = np.ascontiguousarray(cands, KP_DTYPE)
+    sel = np.zeros(max(len(cands), 1), np.int32)
+    n = ctypes.c_int()
+    rc = lib().orc_orb_distribute(P(cands), len(cands), min_x, max_x, min_y, max_y, n_want, P(sel), ctypes.byref(n))
+    assert rc == 0, rc
+    return sel[:n.value].copy()
+
+
+def orientation(level, x, y):
+    """IC_Angle at level positions: (m10, m01, fastAtan2 angle)."""
+    level = np.ascontiguousarray(level, np.uint8)
+    x, y = np.ascontiguousarray(x, np.float32), np.ascontiguousarray(y, np.float32)
+    n = len(x)
+    m10, m01 = np.zeros(n, np.int32), np.zeros(n, np.int32)
+    ang = np.zeros(n, np.float32)
+    lib().orc_orb_orientation(P(level), level.shape[1], level.shape[0], n, P(x), P(y), P(m10), P(m01), P(ang))
+    return m10, m01, ang
+
+
+def describe(blurred, x, y, angle):
+    """computeOrbDescriptor at level positions of a blurred level: [n][32] u8."""
+    blurred = np.ascontiguousarray(blurred, np.uint8)
+    x, y = np.ascontiguousarray(x, np.float32), np.ascontiguousarray(y, np.float32)
+    angle = np.ascontiguousarray(angle, np.float32)
+    desc = np.zeros((len(x), 32), np.uint8)
+    lib().orc_orb_describe(P(blurred), blurred.shape[1], blurred.shape[0], len(x), P(x), P(y), P(angle), P(desc))
+    return desc
+
+
 def extract(img, nfeatures=1000, scale=1.2, nlevels=8, ini=20, mn=7):
     img = np.ascontiguousarray(img, np.uint8)
     h, w = img.shape
@@ -235,6 +279,37 @@ def iforest(pts, trees=50, seed=12345, sample=None):
     rc = lib().orc_iforest_scores(P(pts), n, trees, seed, sample, P(s))
     assert rc == 0
     return s
+
+
+def iforest_try(pts, trees=50, seed=12345, sample=None):
+    """iforest without the success assertion: (ok, scores or None)."""
+    pts = np.ascontiguousarray(pts, np.float32)
+    n = len(pts)
+    sample = n // 2 if sample is None else sample
+    s = np.zeros(n, np.float64)
+    rc = lib().orc_iforest_scores(P(pts), n, trees, seed, sample, P(s))
+    return (True, s) if rc == 0 else (False, None)
+
+
+REF_DIR = os.path.join(HERE, "_ref")
+IFOREST_REF = os.path.join(REF_DIR, "iforest_ref_driver")
+
+
+def reference_tree():
+    """The reference checkout named by BASELINE.json (None where it is absent)."""
+    import json
+    with open(os.path.join(os.path.dirname(HERE), "BASELINE.json")) as f:
+        ref = json.load(f).get("reference_path")
+    return ref if ref and os.path.exists(os.path.join(ref, "include", "isolation_forest.h")) else None
+
+
+def build_ref():
+    """Build oracle/_ref (our drivers over the reference's own headers) where the reference tree
+    is present; returns the driver's path, or None if there is neither a tree nor a binary."""
+    ref = reference_tree()
+    if ref is not None:
+        subprocess.check_call(["make", "-s", "-C", HERE, "ref", "REF=" + ref])
+    return IFOREST_REF if os.path.exists(IFOREST_REF) else None
 
 
 def mt_stream(seed, n):

@@ -94,13 +94,16 @@ def test_gaussian_blur_mechanics():
         assert np.array_equal(orc.blur7(img), _blur7_numpy(img))
 
 
+FAST_ATAN2_BOUND_DEG = 0.3  # cv::fastAtan2 documented accuracy; the ORB definition tests import it
+
+
 def test_fast_atan2_accuracy():
     rng = np.random.default_rng(2)
     for y, x in rng.normal(size=(2000, 2)).astype(np.float32):
         a = orc.fast_atan2(y, x)
         ref = math.degrees(math.atan2(y, x)) % 360.0
         d = abs(a - ref)
-        assert min(d, 360 - d) < 0.3  # cv::fastAtan2 documented accuracy
+        assert min(d, 360 - d) < FAST_ATAN2_BOUND_DEG
     assert orc.fast_atan2(0.0, 0.0) == 0.0
 
 

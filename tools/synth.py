@@ -132,6 +132,49 @@ def frame_stream(n, w=640, h=480, seed=0xEA0, step=0.004, structure=False):
     return frames, poses
 
 
+ORB_CASE_KINDS = ("textured", "noise", "lowcontrast", "flat", "blocky", "checker")
+_orb_case_tex = {}
+
+
+def orb_case(kind, w, h):
+    """One [h][w] u8 image of the ORB definition tests (tests/test_oracle_orb_py.py,
+    tests/test_gpu_orb_definition.py), each kind aimed at one rule of the extraction:
+      textured     a rendered view of the texture: ordinary corners;
+      noise        uniform noise: dense corners, every level quota filled;
+      lowcontrast  noise over 21 grey levels with sparse brighter dots: circle differences
+                   stay below 20 except at the dots, so most cells find nothing at
+                   iniThFAST and take the minThFAST pass;
+      flat         no corner at all;
+      blocky       3x3 blocks of few grey levels: plateaus of equal response next to one
+                   another, which a strict non-maximum rule suppresses together;
+      checker      a regular checkerboard with one dot in every square (the junctions of a
+                   bare checkerboard suppress one another and leave nothing): hundreds of
+                   candidates of identical response, so inside a quadtree node the first wins."""
+    rng = np.random.Generator(np.random.PCG64(0xEA9 + 31 * w + h))
+    if kind == "textured":
+        if 2048 not in _orb_case_tex:
+            _orb_case_tex[2048] = texture(0xEA9, 2048)
+        return render(_orb_case_tex[2048], camera_path(1, w)[0], w, h, K=(0.8 * w, 0.8 * w, 0.5 * w, 0.5 * h))
+    if kind == "noise":
+        return rng.integers(0, 256, (h, w), dtype=np.uint8)
+    if kind == "lowcontrast":
+        img = rng.integers(118, 139, (h, w), dtype=np.uint8)
+        n = w * h // 4000
+        img[rng.integers(0, h, n), rng.integers(0, w, n)] = 200
+        return img
+    if kind == "flat":
+        return np.full((h, w), 128, np.uint8)
+    if kind == "blocky":
+        b = rng.integers(0, 4, (h // 3 + 1, w // 3 + 1)).astype(np.uint8) * 60 + 30
+        return np.ascontiguousarray(np.kron(b, np.ones((3, 3), np.uint8))[:h, :w])
+    if kind == "checker":
+        y, x = np.mgrid[0:h, 0:w]
+        img = np.where(((x // 12) + (y // 12)) % 2 == 0, 90, 150).astype(np.uint8)
+        img[(y % 12 == 6) & (x % 12 == 6)] += 80
+        return img
+    raise ValueError(kind)
+
+
 # ----------------------------------------------------------------------------
 # Association workload (SURVEY.md 8d configs 2-4): objects with point clouds
 # seen along a camera path, YOLO-like boxes, tracked map points per frame.
