@@ -19,6 +19,9 @@
 //                 are resolved in order against the frame features still free (LDS flags), each
 //                 lane holding a strided share: (best, first index, second best) merged across
 //                 the wave; ratio test, TH_LOW;
+//   k_bow_triang  SearchForTriangulation (src/ORBmatcher.cc:657-823): the same node merge and staging, each
+//                 unmatched KF1 feature of a node against the node's unmatched KF2 features with the
+//                 epipolar gates (last candidate wins ties);
 //   k_bow_rot     one workgroup per search: rotation histogram, ComputeThreeMaxima, removal.
 // Every result is integer / exact (the weights are sums of the vocabulary's doubles in the
 // reference's order), so the bar is bit-exact against oracle/bow_ref.cpp.
@@ -304,6 +307,102 @@ __global__ __launch_bounds__(256) void k_bow_search(int cap, SearchSlot K, Searc
   }
 }
 
+// SearchForTriangulation (ORBmatcher.cc:657-823), monocular: per search the fundamental matrix F12, the
+// centre of camera 1 and the pose of keyframe 2, and the level tables of keyframe 2
+struct TriGeom {
+  const float* F12;   // [nsearch][9] row-major
+  const float* Ow1;   // [nsearch][3]
+  const float* Tcw2;  // [nsearch][16]
+  const float* scales;  // [nlevels] mvScaleFactors
+  const float* sigma2;  // [nlevels] mvLevelSigma2
+  float fx, fy, cx, cy;
+  int nlevels;
+};
+
+// One wave per KF1 node, the node of KF2 with the same id found as in k_bow_search and its features'
+// "holds a map point" flags staged in LDS. The reference never sets vbMatched2, so every KF1 feature
+// of the node is independent: a KF2 feature is a candidate when it has no map point, its distance is
+// <= TH_LOW, it lies away from the epipole and on the epipolar line (CheckDistEpipolarLine, :140-157)
+// -- none of which depends on the scan's state -- and `dist > bestDist -> continue` with bestDist set
+// by the accepted candidates makes the answer the smallest distance, the LAST in list order on ties.
+// K1.valid / K2.valid are the has_mp flags here.
+__global__ __launch_bounds__(256) void k_bow_triang(int cap, SearchSlot K1, SearchSlot K2, TriGeom g,
+                                                    int* __restrict__ match12, int* __restrict__ err) {
+  __shared__ uint8_t s_flag[4][NODE_MAXF];
+  const int s = blockIdx.y, w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int j = blockIdx.x * 4 + w;
+  if (j >= K1.nn[s]) return;
+  const size_t so = (size_t)s * cap, ss = (size_t)s * (cap + 1);
+  const int id = K1.ids[so + j];
+  int lo = 0, hi = K2.nn[s];
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (K2.ids[so + mid] < id) lo = mid + 1;
+    else hi = mid;
+  }
+  if (lo >= K2.nn[s] || K2.ids[so + lo] != id) return;
+  const int q0 = K2.start[ss + lo], nq = K2.start[ss + lo + 1] - q0;
+  if (nq > NODE_MAXF) {  // reported per search through nmatches (k_bow_rot)
+    if (lane == 0) atomicOr(&err[s], 1);
+    return;
+  }
+  uint8_t* flag = s_flag[w];
+  for (int q = lane; q < nq; q += 64) flag[q] = K2.valid[so + K2.feats[so + q0 + q]] ? 1 : 0;  // pMP2: skipped
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  // the epipole in image 2: C2 = R2w * Cw + t2w (float dot, the translation added in double)
+  const float* T = g.Tcw2 + 16 * (size_t)s;
+  const float* C = g.Ow1 + 3 * (size_t)s;
+  float C2[3];
+#pragma unroll
+  for (int r = 0; r < 3; r++) {
+    const float t = __fadd_rn(__fadd_rn(__fmul_rn(T[4 * r], C[0]), __fmul_rn(T[4 * r + 1], C[1])),
+                              __fmul_rn(T[4 * r + 2], C[2]));
+    C2[r] = (float)((double)t + (double)T[4 * r + 3]);
+  }
+  const float invz = __fdiv_rn(1.0f, C2[2]);
+  const float ex = __fadd_rn(__fmul_rn(__fmul_rn(g.fx, C2[0]), invz), g.cx);
+  const float ey = __fadd_rn(__fmul_rn(__fmul_rn(g.fy, C2[1]), invz), g.cy);
+  const float* F = g.F12 + 9 * (size_t)s;
+  const int p0 = K1.start[ss + j], p1 = K1.start[ss + j + 1];
+  for (int p = p0; p < p1; p++) {
+    const int idx1 = K1.feats[so + p];
+    if (K1.valid[so + idx1]) continue;  // pMP1: already a map point
+    const eao_keypoint_dev kp1 = K1.kps[so + idx1];
+    // the epipolar line of kp1 in image 2, l = x1' F12 = [a b c]
+    const float a = __fadd_rn(__fadd_rn(__fmul_rn(kp1.x, F[0]), __fmul_rn(kp1.y, F[3])), F[6]);
+    const float b = __fadd_rn(__fadd_rn(__fmul_rn(kp1.x, F[1]), __fmul_rn(kp1.y, F[4])), F[7]);
+    const float c = __fadd_rn(__fadd_rn(__fmul_rn(kp1.x, F[2]), __fmul_rn(kp1.y, F[5])), F[8]);
+    const float den = __fadd_rn(__fmul_rn(a, a), __fmul_rn(b, b));
+    if (den == 0) continue;  // CheckDistEpipolarLine rejects every candidate
+    const uint8_t* d1 = K1.desc + 32 * (so + idx1);
+    const uint4 b0 = *(const uint4*)d1, b1 = *(const uint4*)(d1 + 16);
+    // key = (distance, positions counted from the end): the minimum is the last of the smallest
+    unsigned long long best = ~0ull;
+    for (int q = lane; q < nq; q += 64) {
+      if (flag[q]) continue;
+      const int idx2 = K2.feats[so + q0 + q];
+      const int d = ham32(K2.desc + 32 * (so + idx2), b0, b1);
+      if (d > TH_LOW) continue;
+      const eao_keypoint_dev kp2 = K2.kps[so + idx2];
+      if (kp2.octave < 0 || kp2.octave >= g.nlevels) continue;  // no level table entry
+      const float distex = __fsub_rn(ex, kp2.x), distey = __fsub_rn(ey, kp2.y);
+      if (__fadd_rn(__fmul_rn(distex, distex), __fmul_rn(distey, distey)) < __fmul_rn(100.0f, g.scales[kp2.octave]))
+        continue;
+      const float num = __fadd_rn(__fadd_rn(__fmul_rn(a, kp2.x), __fmul_rn(b, kp2.y)), c);
+      const float dsqr = __fdiv_rn(__fmul_rn(num, num), den);
+      if (!((double)dsqr < 3.84 * (double)g.sigma2[kp2.octave])) continue;
+      const unsigned long long key = ((unsigned long long)d << 32) | (unsigned)(nq - 1 - q);
+      best = key < best ? key : best;
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+      const unsigned long long u = __shfl_xor(best, o, 64);
+      best = u < best ? u : best;
+    }
+    if (lane == 0 && best != ~0ull) match12[so + idx1] = K2.feats[so + q0 + (nq - 1 - (int)(best & 0xffffffffu))];
+  }
+}
+
 __device__ __forceinline__ int rot_bin(float a_kf, float a_f) {
   const float factor = 1.0f / HISTO_LENGTH;
   float rot = __fsub_rn(a_kf, a_f);
@@ -405,6 +504,7 @@ struct VocabEngine {
   double* d_ww = nullptr;             // [max_kps]
   int* d_out = nullptr;               // [max_kps + 16]
   int* d_err = nullptr;
+  float* d_tri = nullptr;             // triangulation search: [32] scale factors, [32] level sigma2, F12 | Ow1 | Tcw2
   int* h_small = nullptr;             // pinned scalars of the single-frame calls
   std::vector<void*> ptrs;
   ~VocabEngine() {
@@ -492,6 +592,7 @@ int eao_vocab_create(int device, int n_nodes, const uint8_t* node_desc, const in
   if ((r = e.alloc(&e.d_ww, sizeof(double) * K)) != hipSuccess) return fail(r);
   if ((r = e.alloc(&e.d_out, sizeof(int) * (K + 16))) != hipSuccess) return fail(r);
   if ((r = e.alloc(&e.d_err, sizeof(int) * B)) != hipSuccess) return fail(r);
+  if ((r = e.alloc(&e.d_tri, sizeof(float) * 96)) != hipSuccess) return fail(r);
   if ((r = hipHostMalloc((void**)&e.h_small, sizeof(int) * 16, 0)) != hipSuccess) return fail(r);
   if (n_nodes > 0) {
     if ((r = hipMemcpy(e.d_vdesc, node_desc, 32 * (size_t)n_nodes, hipMemcpyHostToDevice)) != hipSuccess) return fail(r);
@@ -638,13 +739,80 @@ int eao_search_by_bow_kf_batch_device(eao_vocab* v, float nnratio, int check_ori
   return EAO_OK;
 }
 
+}  // extern "C"
+
+enum { SEARCH_KF_FRAME = 0, SEARCH_KF_KF = 1, SEARCH_TRIANGULATION = 2 };
+
+struct TriHost {  // the triangulation search's extra arguments (host arrays)
+  const eao_camera* cam2;
+  const float *F12, *Ow1, *Tcw2;
+  int nlevels;
+  const float *scale_factors, *level_sigma2;
+};
+
+// the two launches of SearchForTriangulation over nsearch HBM-resident searches; d_geo* and the level
+// tables (e.d_tri: [32] scale factors, [32] level sigma2) are on the device already
+static int triangulation_launch(VocabEngine& e, const eao_camera* cam2, int check_ori, int nsearch, int cap,
+                                const float* d_F12, const float* d_Ow1, const float* d_Tcw2, const int* d_n1,
+                                const SearchSlot& K1, const SearchSlot& K2, int nlevels, int* d_match12,
+                                int* d_nmatches, hipStream_t s) {
+  const TriGeom g{d_F12, d_Ow1, d_Tcw2, e.d_tri, e.d_tri + 32, cam2->fx, cam2->fy, cam2->cx, cam2->cy, nlevels};
+  EAO_HIP_CHECK(hipMemsetAsync(d_match12, 0xff, sizeof(int) * (size_t)nsearch * cap, s));
+  EAO_HIP_CHECK(hipMemsetAsync(e.d_err, 0, sizeof(int) * nsearch, s));
+  hipLaunchKernelGGL(k_bow_triang, dim3((cap + 3) / 4, nsearch), dim3(256), 0, s, cap, K1, K2, g, d_match12,
+                     e.d_err);
+  hipLaunchKernelGGL(k_bow_rot<true>, dim3(nsearch), dim3(256), 0, s, cap, d_n1, K1.kps, K2.kps, check_ori,
+                     d_match12, d_nmatches, e.d_err);
+  EAO_HIP_CHECK(hipGetLastError());
+  return EAO_OK;
+}
+
+extern "C" {
+
+int eao_search_for_triangulation_batch_device(
+    eao_vocab* v, const eao_camera* cam2, int check_ori, int nsearch, int cap, const float* d_F12,
+    const float* d_Ow1, const float* d_Tcw2, const int32_t* d_n1, const eao_keypoint* d_kps1,
+    const uint8_t* d_desc1, const uint8_t* d_has_mp1, const int32_t* d_nn1, const int32_t* d_node_ids1,
+    const int32_t* d_node_start1, const int32_t* d_node_feats1, const eao_keypoint* d_kps2,
+    const uint8_t* d_desc2, const uint8_t* d_has_mp2, const int32_t* d_nn2, const int32_t* d_node_ids2,
+    const int32_t* d_node_start2, const int32_t* d_node_feats2, int nlevels, const float* scale_factors,
+    const float* level_sigma2, int32_t* d_match12, int32_t* d_nmatches, void* stream) {
+  if (!v || !cam2 || nsearch < 0 || cap < 1 || nlevels < 1 || nlevels > 32 || !scale_factors || !level_sigma2 ||
+      (nsearch > 0 && (!d_F12 || !d_Ow1 || !d_Tcw2 || !d_n1 || !d_kps1 || !d_desc1 || !d_has_mp1 || !d_nn1 ||
+                       !d_node_ids1 || !d_node_start1 || !d_node_feats1 || !d_kps2 || !d_desc2 || !d_has_mp2 ||
+                       !d_nn2 || !d_node_ids2 || !d_node_start2 || !d_node_feats2 || !d_match12 || !d_nmatches))) {
+    set_error("eao_search_for_triangulation_batch_device: bad arguments (nlevels outside [1, 32] or null buffer)");
+    return EAO_E_ARG;
+  }
+  if (nsearch > v->e.max_batch || cap > v->e.max_kps) {
+    set_error("eao_search_for_triangulation_batch_device: more searches than max_batch or slots larger than max_kps");
+    return EAO_E_CAPACITY;
+  }
+  if (nsearch == 0) return EAO_OK;
+  VocabEngine& e = v->e;
+  EAO_HIP_CHECK(hipSetDevice(e.dev));
+  hipStream_t s = stream ? (hipStream_t)stream : e.stream;
+  EAO_HIP_CHECK(hipMemcpyAsync(e.d_tri, scale_factors, sizeof(float) * nlevels, hipMemcpyHostToDevice, s));
+  EAO_HIP_CHECK(hipMemcpyAsync(e.d_tri + 32, level_sigma2, sizeof(float) * nlevels, hipMemcpyHostToDevice, s));
+  return triangulation_launch(e, cam2, check_ori, nsearch, cap, d_F12, d_Ow1, d_Tcw2, d_n1,
+                              SearchSlot{(const eao_keypoint_dev*)d_kps1, d_desc1, d_has_mp1, d_nn1, d_node_ids1,
+                                         d_node_start1, d_node_feats1},
+                              SearchSlot{(const eao_keypoint_dev*)d_kps2, d_desc2, d_has_mp2, d_nn2, d_node_ids2,
+                                         d_node_start2, d_node_feats2},
+                              nlevels, d_match12, d_nmatches, s);
+}
+
+}  // extern "C"
+
 // one search of either kind on host buffers: side 1 (keyframe / KF1) and side 2 (frame / KF2)
 // staged into the handle's two slots, the batched path on one search, the result back
-static int search_single(eao_vocab* v, bool kfkf, const char* name, float nnratio, int check_ori, int n1,
+static int search_single(eao_vocab* v, int kind, const char* name, float nnratio, int check_ori, int n1,
                          const eao_keypoint* kps1, const uint8_t* desc1, const uint8_t* valid1, int nn1,
                          const int32_t* ids1, const int32_t* st1, const int32_t* ft1, int n2,
                          const eao_keypoint* kps2, const uint8_t* desc2, const uint8_t* valid2, int nn2,
-                         const int32_t* ids2, const int32_t* st2, const int32_t* ft2, int32_t* out) {
+                         const int32_t* ids2, const int32_t* st2, const int32_t* ft2, int32_t* out,
+                         const TriHost* tri = nullptr) {
+  const bool kfkf = kind != SEARCH_KF_FRAME;  // both sides keyframes: flags on side 2, result indexed by side 1
   if (!v || n1 < 0 || n2 < 0 || n1 > v->e.max_kps || n2 > v->e.max_kps || nn1 < 0 || nn2 < 0 || nn1 > n1 ||
       nn2 > n2 || !out || (n1 > 0 && (!kps1 || !desc1 || !valid1)) ||
       (n2 > 0 && (!kps2 || !desc2 || (kfkf && !valid2))) || (nn1 > 0 && (!ids1 || !st1 || !ft1)) ||
@@ -710,7 +878,22 @@ static int search_single(eao_vocab* v, bool kfkf, const char* name, float nnrati
   if (rc) return rc;
   const eao_keypoint* k1 = (const eao_keypoint*)e.d_kps;
   const eao_keypoint* k2 = (const eao_keypoint*)(e.d_kps + K);
-  if (kfkf)
+  float g[96] = {0};  // lives until the stream is synchronised below
+  if (kind == SEARCH_TRIANGULATION) {
+    // level tables and the search's geometry behind them in d_tri
+    std::memcpy(g, tri->scale_factors, sizeof(float) * tri->nlevels);
+    std::memcpy(g + 32, tri->level_sigma2, sizeof(float) * tri->nlevels);
+    std::memcpy(g + 64, tri->F12, sizeof(float) * 9);
+    std::memcpy(g + 73, tri->Ow1, sizeof(float) * 3);
+    std::memcpy(g + 76, tri->Tcw2, sizeof(float) * 16);
+    EAO_HIP_CHECK(hipMemcpyAsync(e.d_tri, g, sizeof(g), hipMemcpyHostToDevice, s));
+    rc = triangulation_launch(e, tri->cam2, check_ori, 1, K, e.d_tri + 64, e.d_tri + 73, e.d_tri + 76, I1 + 3 * K + 5,
+                              SearchSlot{(const eao_keypoint_dev*)k1, e.d_desc, e.d_valid, I1 + 3 * K + 4, I1, I1 + K,
+                                         I1 + 2 * K + 1},
+                              SearchSlot{(const eao_keypoint_dev*)k2, e.d_desc + 32 * (size_t)K, e.d_valid + K,
+                                         I2 + 3 * K + 4, I2, I2 + K, I2 + 2 * K + 1},
+                              tri->nlevels, e.d_out, e.d_out + K, s);
+  } else if (kfkf)
     rc = eao_search_by_bow_kf_batch_device(v, nnratio, check_ori, 1, K, I1 + 3 * K + 5, k1, e.d_desc, e.d_valid,
                                            I1 + 3 * K + 4, I1, I1 + K, I1 + 2 * K + 1, k2, e.d_desc + 32 * (size_t)K,
                                            e.d_valid + K, I2 + 3 * K + 4, I2, I2 + K, I2 + 2 * K + 1, e.d_out,
@@ -731,14 +914,16 @@ static int search_single(eao_vocab* v, bool kfkf, const char* name, float nnrati
   return nm;
 }
 
+extern "C" {
+
 int eao_search_by_bow(eao_vocab* v, float nnratio, int check_ori, int n_kf, const eao_keypoint* kf_kps,
                       const uint8_t* kf_desc, const uint8_t* kf_mp_valid, int kf_nn,
                       const int32_t* kf_node_ids, const int32_t* kf_node_start,
                       const int32_t* kf_node_feats, int n_f, const eao_keypoint* f_kps,
                       const uint8_t* f_desc, int f_nn, const int32_t* f_node_ids,
                       const int32_t* f_node_start, const int32_t* f_node_feats, int32_t* f_match) {
-  return search_single(v, false, "eao_search_by_bow", nnratio, check_ori, n_kf, kf_kps, kf_desc, kf_mp_valid, kf_nn,
-                       kf_node_ids, kf_node_start, kf_node_feats, n_f, f_kps, f_desc, nullptr, f_nn, f_node_ids,
+  return search_single(v, SEARCH_KF_FRAME, "eao_search_by_bow", nnratio, check_ori, n_kf, kf_kps, kf_desc, kf_mp_valid,
+                       kf_nn, kf_node_ids, kf_node_start, kf_node_feats, n_f, f_kps, f_desc, nullptr, f_nn, f_node_ids,
                        f_node_start, f_node_feats, f_match);
 }
 
@@ -747,9 +932,27 @@ int eao_search_by_bow_kf(eao_vocab* v, float nnratio, int check_ori, int n1, con
                          const int32_t* node_start1, const int32_t* node_feats1, int n2, const eao_keypoint* kps2,
                          const uint8_t* desc2, const uint8_t* valid2, int nn2, const int32_t* node_ids2,
                          const int32_t* node_start2, const int32_t* node_feats2, int32_t* match12) {
-  return search_single(v, true, "eao_search_by_bow_kf", nnratio, check_ori, n1, kps1, desc1, valid1, nn1, node_ids1,
+  return search_single(v, SEARCH_KF_KF, "eao_search_by_bow_kf", nnratio, check_ori, n1, kps1, desc1, valid1, nn1, node_ids1,
                        node_start1, node_feats1, n2, kps2, desc2, valid2, nn2, node_ids2, node_start2, node_feats2,
                        match12);
+}
+
+int eao_search_for_triangulation(eao_vocab* v, const eao_camera* cam2, const float* F12, const float* Ow1,
+                                 const float* Tcw2, int check_ori, int n1, const eao_keypoint* kps1,
+                                 const uint8_t* desc1, const uint8_t* has_mp1, int nn1, const int32_t* node_ids1,
+                                 const int32_t* node_start1, const int32_t* node_feats1, int n2,
+                                 const eao_keypoint* kps2, const uint8_t* desc2, const uint8_t* has_mp2, int nn2,
+                                 const int32_t* node_ids2, const int32_t* node_start2, const int32_t* node_feats2,
+                                 int nlevels, const float* scale_factors, const float* level_sigma2,
+                                 int32_t* match12) {
+  if (!cam2 || !F12 || !Ow1 || !Tcw2 || nlevels < 1 || nlevels > 32 || !scale_factors || !level_sigma2) {
+    set_error("eao_search_for_triangulation: bad arguments (nlevels outside [1, 32] or null buffer)");
+    return EAO_E_ARG;
+  }
+  const TriHost tri{cam2, F12, Ow1, Tcw2, nlevels, scale_factors, level_sigma2};
+  return search_single(v, SEARCH_TRIANGULATION, "eao_search_for_triangulation", 0.0f, check_ori, n1, kps1, desc1,
+                       has_mp1, nn1, node_ids1, node_start1, node_feats1, n2, kps2, desc2, has_mp2, nn2, node_ids2,
+                       node_start2, node_feats2, match12, &tri);
 }
 
 }  // extern "C"

@@ -41,7 +41,7 @@ class MatchEngine {
   int* d_i32b = nullptr;              // [max_kps]
   int* d_out = nullptr;               // [max_kps + 16]
   float* d_T = nullptr;               // [16 * batch]
-  float* d_scales = nullptr;          // [32]
+  float* d_scales = nullptr;          // [32] scale factors, [32] inverse level sigma2 (Fuse)
   float* d_geo = nullptr;             // [max_kps][4] per-map-point projection (keyframe search)
   // motion search candidates: MK smallest keys / rotation bins / count per (pair, query)
   unsigned long long* d_ckeys = nullptr;

@@ -1,6 +1,9 @@
 // match.hip -- ORB matching on gfx950: the MI355X replacement of the Frame
 // grid (reference src/Frame.cc:351-513) and ORBmatcher searches
-// (src/ORBmatcher.cc:45-137, 405-520, 1328-1663).
+// (src/ORBmatcher.cc:45-137, 405-520, 1328-1663), and of the projection searches into a
+// keyframe of the mapping and loop threads (Fuse, Fuse with a Sim3, SearchBySim3:
+// src/ORBmatcher.cc:825-1326 with KeyFrame::GetFeaturesInArea, src/KeyFrame.cc:612-651;
+// monocular, the stereo branch of Fuse is not built).
 //
 // Sequential first-wins semantics are kept exactly: each
 // search runs one wave per frame pair that walks the queries in reference
@@ -1189,6 +1192,164 @@ __global__ void k_hamming_pairs(const uint8_t* __restrict__ q, const uint8_t* __
   if (i < n) out[i] = hamming256(q + 32 * (long long)qi[i], t + 32 * (long long)ti[i]);
 }
 
+// ---- projection searches into a keyframe: ORBmatcher::Fuse (ORBmatcher.cc:825-975),
+// Fuse with a Sim3 (:977-1100) and the two halves of SearchBySim3 (:1102-1326), monocular.
+// A point's search reads the keyframe's keypoints / descriptors and the point's own data only
+// (the side effects of Fuse stay with the caller), so the points of a call are independent:
+// one wave per point. Every lane projects the point and applies the gates; the lanes then
+// share the cells of KeyFrame::GetFeaturesInArea (KeyFrame.cc:612-651: 64x48 grid, ix outer,
+// iy inner, cells in index order) and the wave keeps the smallest key (distance, cell in walk
+// order, index): the reference's strict-< scan, the first keypoint in walk order on ties.
+enum { KF_FUSE = 0, KF_FUSE_SIM3 = 1, KF_SIM3 = 2 };
+
+// one search, or a batch (search f: point slot f of stride qs, keyframe slot f of stride cs,
+// pose f); a single call passes null counts and zero strides
+struct KfProj {
+  const float* T;   // [16] per search. FUSE: Tcw; FUSE_SIM3: [Rcw | tcw] of the decomposed Scw;
+                    // SIM3: the similarity between the two cameras, [sR | t]
+  const float* T0;  // SIM3: the pose of the points' own keyframe, applied first
+  const uint8_t* valid;
+  const uint8_t* skip;  // SIM3: vbAlreadyMatched of the points' side
+  const float* pos;
+  const float* nrm;
+  const float* mind;
+  const float* maxd;
+  const uint8_t* mdesc;
+  const eao_keypoint_dev* K;
+  const uint8_t* D;
+  const int* GS;
+  const int* GI;
+  const float* scales;
+  const float* invsig2;  // FUSE: mvInvLevelSigma2
+  int* best_idx;
+  int* best_dist;
+  int* nfound;  // += points with best_idx >= 0 (may be null)
+  const int* nq;
+  int n_mp, qs, cs, nlevels;
+  float th, logsf;
+};
+
+template <int MODE>
+__global__ __launch_bounds__(256) void k_kf_project(CamDev cam, KfProj a) {
+  const int f = blockIdx.y, lane = threadIdx.x & 63;
+  const int i = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int n_mp = a.nq ? min(a.nq[f], a.qs) : a.n_mp;
+  if (i >= n_mp) return;  // the whole wave
+  const long long qo = (long long)f * a.qs + i, co = (long long)f * a.cs;
+  const eao_keypoint_dev* CK = a.K + co;
+  const uint8_t* CD = a.D + 32 * co;
+  const int* GS = a.GS + (long long)f * (GRID_CELLS + 1);
+  const int* GI = a.GI + co;
+  float T[16];
+  for (int k = 0; k < 16; k++) T[k] = a.T[16 * f + k];
+  bool ok = a.valid[qo] != 0;
+  if (MODE == KF_SIM3 && a.skip[qo]) ok = false;
+  float u = 0.f, v = 0.f, r = 0.f;
+  int lvl = 0;
+  if (ok) {
+    ok = false;
+    const float* P = a.pos + 3 * qo;
+    float Pc[3];
+    if (MODE == KF_SIM3) {
+      float T0[16], P1[3];
+      for (int k = 0; k < 16; k++) T0[k] = a.T0[16 * f + k];
+      transform_point(T0, P, P1);
+      transform_point(T, P1, Pc);
+    } else {
+      transform_point(T, P, Pc);
+    }
+    do {
+      if (Pc[2] < 0.0f) break;
+      // Fuse divides in float (1/z), the Sim3 forms in double (1.0/z)
+      const float invz = MODE == KF_FUSE ? fdiv(1.0f, Pc[2]) : (float)(1.0 / (double)Pc[2]);
+      u = fadd(fmul(cam.fx, fmul(Pc[0], invz)), cam.cx);
+      v = fadd(fmul(cam.fy, fmul(Pc[1], invz)), cam.cy);
+      if (!(u >= cam.minX && u < cam.maxX && v >= cam.minY && v < cam.maxY)) break;  // KeyFrame::IsInImage
+      const float maxDistance = fmul(1.2f, a.maxd[qo]);
+      const float minDistance = fmul(0.8f, a.mind[qo]);
+      float dist3D;
+      if (MODE == KF_SIM3) {
+        double s = 0;
+        for (int k = 0; k < 3; k++) s = __dadd_rn(s, __dmul_rn((double)Pc[k], (double)Pc[k]));
+        dist3D = (float)sqrt(s);
+        if (dist3D < minDistance || dist3D > maxDistance) break;
+      } else {
+        float PO[3];  // p3Dw - Ow, Ow = -Rcw^T tcw (transposed gemm operand, see k_frustum)
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+          double s = (double)T[c] * (double)T[3];
+          s = __dadd_rn(s, (double)T[4 + c] * (double)T[7]);
+          s = __dadd_rn(s, (double)T[8 + c] * (double)T[11]);
+          PO[c] = fsub(P[c], (float)(s * -1.0));
+        }
+        double s = 0, dot = 0;
+        for (int k = 0; k < 3; k++) s = __dadd_rn(s, __dmul_rn((double)PO[k], (double)PO[k]));
+        dist3D = (float)sqrt(s);
+        if (dist3D < minDistance || dist3D > maxDistance) break;
+        const float* N = a.nrm + 3 * qo;
+        for (int k = 0; k < 3; k++) dot = __dadd_rn(dot, __dmul_rn((double)PO[k], (double)N[k]));
+        if (dot < 0.5 * (double)dist3D) break;
+      }
+      const float ratio = fdiv(a.maxd[qo], dist3D);
+      lvl = (int)ceilf(fdiv((float)log((double)ratio), a.logsf));
+      lvl = min(max(lvl, 0), a.nlevels - 1);  // Q13 clamp, as k_keyframe_cand
+      r = fmul(a.th, a.scales[lvl]);
+      ok = true;
+    } while (0);
+  }
+  unsigned long long best = KEY_NONE;
+  if (ok) {
+    const Window w = window_cells(cam, u, v, r);
+    if (!w.empty) {
+      const int ncy = w.y1 - w.y0 + 1, ncell = (w.x1 - w.x0 + 1) * ncy;
+      const uint8_t* d = a.mdesc + 32 * qo;
+      for (int ck = lane; ck < ncell; ck += 64) {
+        const int cell = (w.x0 + ck / ncy) * GRID_ROWS + w.y0 + ck % ncy;
+        for (int q = GS[cell]; q < GS[cell + 1]; q++) {
+          const int i2 = GI[q];
+          const eao_keypoint_dev& kp = CK[i2];
+          if (!(fabsf(fsub(kp.x, u)) < r && fabsf(fsub(kp.y, v)) < r)) continue;
+          if (kp.octave < lvl - 1 || kp.octave > lvl) continue;
+          if (MODE == KF_FUSE) {
+            if (kp.octave < 0) continue;  // no level table entry (octaves are in [0, nlevels))
+            const float ex = fsub(u, kp.x), ey = fsub(v, kp.y);
+            const float e2 = fadd(fmul(ex, ex), fmul(ey, ey));
+            if ((double)fmul(e2, a.invsig2[kp.octave]) > 5.99) continue;
+          }
+          const unsigned long long key = make_key(hamming256(d, CD + 32 * (long long)i2), ck, i2);
+          best = key < best ? key : best;
+        }
+      }
+    }
+  }
+  best = wave_min_u64(best);
+  if (lane == 0) {
+    int bd = 256, bi = -1;
+    if (best != KEY_NONE) {
+      bd = key_dist(best);
+      if (bd <= (MODE == KF_SIM3 ? TH_HIGH : TH_LOW)) bi = key_idx(best);
+    }
+    a.best_idx[qo] = bi;
+    a.best_dist[qo] = bd;
+    if (bi >= 0 && a.nfound) atomicAdd(a.nfound + f, 1);
+  }
+}
+
+// the agreement check of SearchBySim3 (ORBmatcher.cc:1306-1323): one workgroup
+__global__ __launch_bounds__(256) void k_sim3_agree(int n1, int n2, const int* __restrict__ m1,
+                                                    const int* __restrict__ m2, int* __restrict__ match12,
+                                                    int* __restrict__ nfound) {
+  int c = 0;
+  for (int i1 = threadIdx.x; i1 < n1; i1 += 256) {
+    const int idx2 = m1[i1];
+    const bool agree = idx2 >= 0 && idx2 < n2 && m2[idx2] == i1;
+    match12[i1] = agree ? idx2 : -1;
+    c += agree ? 1 : 0;
+  }
+  c = wave_sum(c);
+  if ((threadIdx.x & 63) == 0 && c) atomicAdd(nfound, c);
+}
+
 // ================================================================ host
 int MatchEngine::init(int device, int mk, int mb) {
   dev = device;
@@ -1214,7 +1375,7 @@ int MatchEngine::init(int device, int mk, int mb) {
   EAO_HIP_CHECK(hipMalloc(&d_i32b, sizeof(int) * mk * 2));
   EAO_HIP_CHECK(hipMalloc(&d_out, sizeof(int) * (mk * 2 + 16)));
   EAO_HIP_CHECK(hipMalloc(&d_T, sizeof(float) * 16 * 2));
-  EAO_HIP_CHECK(hipMalloc(&d_scales, sizeof(float) * 32));
+  EAO_HIP_CHECK(hipMalloc(&d_scales, sizeof(float) * 64));  // scale factors | inverse level sigma2
   EAO_HIP_CHECK(hipMalloc(&d_geo, sizeof(float) * 4 * (size_t)mk * max_batch));
   EAO_HIP_CHECK(hipMalloc(&d_ckeys, sizeof(unsigned long long) * MK * (size_t)mk * max_batch));
   EAO_HIP_CHECK(hipMalloc(&d_cbins, (size_t)MK * mk * max_batch));
@@ -1652,6 +1813,307 @@ int eao_match_init(eao_matcher* m, const eao_camera* cam, float nnratio, int che
   EAO_HIP_CHECK(hipStreamSynchronize(s));
   EAO_HIP_CHECK(hipMemcpy(&nm, e.d_out + 2 * K, sizeof(int), hipMemcpyDeviceToHost));
   return nm;
+}
+
+}  // extern "C"
+
+// ---- the keyframe matchers of the mapping and loop threads (Fuse, Fuse with a Sim3, SearchBySim3)
+template <int MODE>
+static void launch_kf_project(const CamDev& cd, const KfProj& a, int nslots, int qmax, hipStream_t s) {
+  hipLaunchKernelGGL(k_kf_project<MODE>, dim3((qmax + 3) / 4, nslots), dim3(256), 0, s, cd, a);
+}
+
+// one Fuse-type search on host buffers: the inputs packed into the pinned staging image and copied
+// over at once, indices / distances / the count back through pinned memory. T16 is the pose the
+// kernel projects with (Tcw, or [Rcw | tcw] of the decomposed Scw).
+static int fuse_single(eao_matcher* m, int mode, const char* name, const eao_camera* cam, const float* T16, float th,
+                       int n_mp, const uint8_t* mp_valid, const float* mp_pos, const float* mp_normal,
+                       const float* mp_min_dist, const float* mp_max_dist, const uint8_t* mp_desc, float logsf,
+                       int n_kf, const eao_keypoint* kf_kps, const uint8_t* kf_desc, int nlevels,
+                       const float* scale_factors, const float* inv_sigma2, int32_t* best_idx,
+                       int32_t* best_dist) {
+  if (!m || !cam || !T16 || n_mp < 0 || n_kf < 0 || nlevels < 1 || nlevels > 32 || !scale_factors ||
+      (mode == KF_FUSE && !inv_sigma2) ||
+      (n_mp > 0 && (!mp_valid || !mp_pos || !mp_normal || !mp_min_dist || !mp_max_dist || !mp_desc || !best_idx ||
+                    !best_dist)) ||
+      (n_kf > 0 && (!kf_kps || !kf_desc))) {
+    set_error(std::string(name) + ": bad arguments (negative size, nlevels outside [1, 32] or null buffer)");
+    return EAO_E_ARG;
+  }
+  MatchEngine& e = m->e;
+  const int K = e.max_kps;
+  if (n_mp > K || n_kf > K) {
+    set_error(std::string(name) + ": more points or keypoints than max_kps");
+    return EAO_E_CAPACITY;
+  }
+  if (n_mp == 0) return 0;
+  EAO_HIP_CHECK(hipSetDevice(e.dev));
+  hipStream_t s = e.stream;
+  HostStage& st = e.stage;
+  float lv[64] = {0};
+  std::memcpy(lv, scale_factors, sizeof(float) * nlevels);
+  if (inv_sigma2) std::memcpy(lv + 32, inv_sigma2, sizeof(float) * nlevels);
+  EAO_HIP_CHECK(st.reserve((size_t)n_kf * (sizeof(eao_keypoint) + 32) + (size_t)n_mp * (1 + 12 + 12 + 4 + 4 + 32) +
+                           sizeof(lv) + 64 + 16 * 12));
+  const size_t o_kps = st.put(kf_kps, sizeof(eao_keypoint) * n_kf), o_desc = st.put(kf_desc, (size_t)32 * n_kf);
+  const size_t o_val = st.put(mp_valid, n_mp), o_pos = st.put(mp_pos, sizeof(float) * 3 * n_mp);
+  const size_t o_nrm = st.put(mp_normal, sizeof(float) * 3 * n_mp), o_min = st.put(mp_min_dist, sizeof(float) * n_mp);
+  const size_t o_max = st.put(mp_max_dist, sizeof(float) * n_mp), o_md = st.put(mp_desc, (size_t)32 * n_mp);
+  const size_t o_T = st.put(T16, sizeof(float) * 16), o_lv = st.put(lv, sizeof(lv));
+  EAO_HIP_CHECK(st.upload(s));
+  EAO_HIP_CHECK(hipMemsetAsync(e.d_out + 2 * K, 0, sizeof(int), s));
+  const CamDev cd = make_cam(*cam);
+  const eao_keypoint_dev* dk = st.dev<const eao_keypoint_dev>(o_kps);
+  int rc = e.build_grid(cd, dk, nullptr, n_kf, std::max(n_kf, 1), 1, s);
+  if (rc) return rc;
+  KfProj a{};
+  a.T = st.dev<const float>(o_T);
+  a.valid = st.dev<const uint8_t>(o_val);
+  a.pos = st.dev<const float>(o_pos);
+  a.nrm = st.dev<const float>(o_nrm);
+  a.mind = st.dev<const float>(o_min);
+  a.maxd = st.dev<const float>(o_max);
+  a.mdesc = st.dev<const uint8_t>(o_md);
+  a.K = dk;
+  a.D = st.dev<const uint8_t>(o_desc);
+  a.GS = e.d_gstart;
+  a.GI = e.d_gitems;
+  a.scales = st.dev<const float>(o_lv);
+  a.invsig2 = a.scales + 32;
+  a.best_idx = e.d_out;
+  a.best_dist = e.d_out + K;
+  a.nfound = e.d_out + 2 * K;
+  a.n_mp = n_mp;
+  a.nlevels = nlevels;
+  a.th = th;
+  a.logsf = logsf;
+  if (mode == KF_FUSE)
+    launch_kf_project<KF_FUSE>(cd, a, 1, n_mp, s);
+  else
+    launch_kf_project<KF_FUSE_SIM3>(cd, a, 1, n_mp, s);
+  EAO_HIP_CHECK(hipGetLastError());
+  EAO_HIP_CHECK(e.res.reserve(sizeof(int) * (2 * (size_t)n_mp + 1)));
+  int* r = (int*)e.res.h;
+  EAO_HIP_CHECK(hipMemcpyAsync(r, e.d_out, sizeof(int) * n_mp, hipMemcpyDeviceToHost, s));
+  EAO_HIP_CHECK(hipMemcpyAsync(r + n_mp, e.d_out + K, sizeof(int) * n_mp, hipMemcpyDeviceToHost, s));
+  EAO_HIP_CHECK(hipMemcpyAsync(r + 2 * n_mp, e.d_out + 2 * K, sizeof(int), hipMemcpyDeviceToHost, s));
+  EAO_HIP_CHECK(hipStreamSynchronize(s));
+  std::memcpy(best_idx, r, sizeof(int) * n_mp);
+  std::memcpy(best_dist, r + n_mp, sizeof(int) * n_mp);
+  return r[2 * n_mp];
+}
+
+extern "C" {
+
+int eao_match_fuse(eao_matcher* m, const eao_camera* cam, const float* Tcw, float th, int n_mp,
+                   const uint8_t* mp_valid, const float* mp_pos, const float* mp_normal,
+                   const float* mp_min_dist, const float* mp_max_dist, const uint8_t* mp_desc,
+                   float log_scale_factor, int n_kf, const eao_keypoint* kf_kps, const uint8_t* kf_desc,
+                   int nlevels, const float* scale_factors, const float* inv_level_sigma2, int32_t* best_idx,
+                   int32_t* best_dist) {
+  return fuse_single(m, KF_FUSE, "eao_match_fuse", cam, Tcw, th, n_mp, mp_valid, mp_pos, mp_normal, mp_min_dist,
+                     mp_max_dist, mp_desc, log_scale_factor, n_kf, kf_kps, kf_desc, nlevels, scale_factors,
+                     inv_level_sigma2, best_idx, best_dist);
+}
+
+int eao_match_fuse_sim3(eao_matcher* m, const eao_camera* cam, const float* Scw, float th, int n_mp,
+                        const uint8_t* mp_valid, const float* mp_pos, const float* mp_normal,
+                        const float* mp_min_dist, const float* mp_max_dist, const uint8_t* mp_desc,
+                        float log_scale_factor, int n_kf, const eao_keypoint* kf_kps, const uint8_t* kf_desc,
+                        int nlevels, const float* scale_factors, int32_t* best_idx, int32_t* best_dist) {
+  float T[16] = {0};
+  if (Scw) {
+    // Decompose Scw (ORBmatcher.cc:985-989): scw = sqrt(row0 . row0) (Mat::dot in double), Rcw = sRcw / scw and
+    // tcw = t / scw (a float multiply by (float)(1 / scw)); Ow follows in the kernel from [Rcw | tcw]
+    double d = 0;
+    for (int k = 0; k < 3; k++) d += (double)Scw[k] * (double)Scw[k];
+    const float scw = (float)std::sqrt(d);
+    const float inv = (float)(1.0 / (double)scw);
+    for (int r = 0; r < 3; r++)
+      for (int c = 0; c < 4; c++) T[4 * r + c] = Scw[4 * r + c] * inv;
+    T[15] = 1.0f;
+  }
+  return fuse_single(m, KF_FUSE_SIM3, "eao_match_fuse_sim3", cam, Scw ? T : nullptr, th, n_mp, mp_valid, mp_pos,
+                     mp_normal, mp_min_dist, mp_max_dist, mp_desc, log_scale_factor, n_kf, kf_kps, kf_desc, nlevels,
+                     scale_factors, nullptr, best_idx, best_dist);
+}
+
+int eao_match_sim3(eao_matcher* m, const eao_camera* cam, const float* Tcw1, const float* Tcw2, float s12,
+                   const float* R12, const float* t12, float th, int n1, const eao_keypoint* kps1,
+                   const uint8_t* desc1, const uint8_t* mp_valid1, const float* mp_pos1,
+                   const float* mp_min_dist1, const float* mp_max_dist1, const uint8_t* mp_desc1,
+                   const uint8_t* already_matched1, int n2, const eao_keypoint* kps2, const uint8_t* desc2,
+                   const uint8_t* mp_valid2, const float* mp_pos2, const float* mp_min_dist2,
+                   const float* mp_max_dist2, const uint8_t* mp_desc2, const uint8_t* already_matched2,
+                   float log_scale_factor, int nlevels, const float* scale_factors, int32_t* match12) {
+  if (!m || !cam || !Tcw1 || !Tcw2 || !R12 || !t12 || n1 < 0 || n2 < 0 || nlevels < 1 || nlevels > 32 ||
+      !scale_factors ||
+      (n1 > 0 && (!kps1 || !desc1 || !mp_valid1 || !mp_pos1 || !mp_min_dist1 || !mp_max_dist1 || !mp_desc1 ||
+                  !already_matched1 || !match12)) ||
+      (n2 > 0 && (!kps2 || !desc2 || !mp_valid2 || !mp_pos2 || !mp_min_dist2 || !mp_max_dist2 || !mp_desc2 ||
+                  !already_matched2))) {
+    set_error("eao_match_sim3: bad arguments (negative size, nlevels outside [1, 32] or null buffer)");
+    return EAO_E_ARG;
+  }
+  MatchEngine& e = m->e;
+  const int K = e.max_kps;
+  if (n1 > K || n2 > K) {
+    set_error("eao_match_sim3: more keypoints than max_kps");
+    return EAO_E_CAPACITY;
+  }
+  if (n1 == 0) return 0;
+  // sR12 = s12 * R12, sR21 = (1.0 / s12) * R12.t(), t21 = -sR21 * t12 (ORBmatcher.cc:1119-1121): the scalings
+  // are float multiplies by (float)alpha, the 3x3 . 3x1 product a float dot
+  float S[4][16] = {{0}};  // Tcw1, Tcw2, S21 = [sR21 | t21], S12 = [sR12 | t12]
+  std::memcpy(S[0], Tcw1, sizeof(float) * 16);
+  std::memcpy(S[1], Tcw2, sizeof(float) * 16);
+  const float inv = (float)(1.0 / (double)s12);
+  for (int r = 0; r < 3; r++) {
+    for (int c = 0; c < 3; c++) {
+      S[3][4 * r + c] = R12[3 * r + c] * s12;
+      S[2][4 * r + c] = R12[3 * c + r] * inv;
+    }
+    S[3][4 * r + 3] = t12[r];
+  }
+  for (int r = 0; r < 3; r++) {
+    const float dot = S[2][4 * r] * t12[0] + S[2][4 * r + 1] * t12[1] + S[2][4 * r + 2] * t12[2];
+    S[2][4 * r + 3] = (float)((double)dot * -1.0);
+  }
+  S[2][15] = S[3][15] = 1.0f;
+  EAO_HIP_CHECK(hipSetDevice(e.dev));
+  hipStream_t s = e.stream;
+  // both keyframes in two slots of stride C: one grid launch, slot k the grid of keyframe k + 1
+  const int C = std::min((std::max(std::max(n1, n2), 1) + 63) & ~63, K);
+  const int counts[4] = {n1, n2, 0, 0};
+  float lv[32] = {0};
+  std::memcpy(lv, scale_factors, sizeof(float) * nlevels);
+  HostStage& st = e.stage;
+  const size_t kb = sizeof(eao_keypoint);
+  EAO_HIP_CHECK(st.reserve(2 * (size_t)C * (kb + 32) + ((size_t)n1 + n2) * (2 + 12 + 8 + 32) + sizeof(S) + sizeof(lv) +
+                           sizeof(counts) + 16 * 20));
+  const size_t o_kps = st.put(nullptr, 2 * C * kb);
+  std::memcpy(st.h + o_kps, kps1, kb * n1);
+  std::memcpy(st.h + o_kps + kb * C, kps2, kb * n2);
+  const size_t o_desc = st.put(nullptr, 2 * (size_t)C * 32);
+  std::memcpy(st.h + o_desc, desc1, (size_t)n1 * 32);
+  std::memcpy(st.h + o_desc + (size_t)C * 32, desc2, (size_t)n2 * 32);
+  const size_t o_v1 = st.put(mp_valid1, n1), o_a1 = st.put(already_matched1, n1);
+  const size_t o_p1 = st.put(mp_pos1, sizeof(float) * 3 * n1), o_n1 = st.put(mp_min_dist1, sizeof(float) * n1);
+  const size_t o_x1 = st.put(mp_max_dist1, sizeof(float) * n1), o_d1 = st.put(mp_desc1, (size_t)32 * n1);
+  const size_t o_v2 = st.put(mp_valid2, n2), o_a2 = st.put(already_matched2, n2);
+  const size_t o_p2 = st.put(mp_pos2, sizeof(float) * 3 * n2), o_n2 = st.put(mp_min_dist2, sizeof(float) * n2);
+  const size_t o_x2 = st.put(mp_max_dist2, sizeof(float) * n2), o_d2 = st.put(mp_desc2, (size_t)32 * n2);
+  const size_t o_S = st.put(S, sizeof(S)), o_lv = st.put(lv, sizeof(lv)), o_cnt = st.put(counts, sizeof(counts));
+  EAO_HIP_CHECK(st.upload(s));
+  EAO_HIP_CHECK(hipMemsetAsync(e.d_out + 2 * K, 0, sizeof(int), s));
+  const CamDev cd = make_cam(*cam);
+  const eao_keypoint_dev* dk = st.dev<const eao_keypoint_dev>(o_kps);
+  int rc = e.build_grid(cd, dk, st.dev<const int>(o_cnt), 0, C, 2, s);
+  if (rc) return rc;
+  const float* dS = st.dev<const float>(o_S);
+  KfProj a{};
+  a.scales = st.dev<const float>(o_lv);
+  a.nlevels = nlevels;
+  a.th = th;
+  a.logsf = log_scale_factor;
+  // KF1's points into KF2: vnMatch1 in d_out[0, n1), distances in d_i32
+  a.T0 = dS;
+  a.T = dS + 32;
+  a.valid = st.dev<const uint8_t>(o_v1);
+  a.skip = st.dev<const uint8_t>(o_a1);
+  a.pos = st.dev<const float>(o_p1);
+  a.mind = st.dev<const float>(o_n1);
+  a.maxd = st.dev<const float>(o_x1);
+  a.mdesc = st.dev<const uint8_t>(o_d1);
+  a.K = dk + C;
+  a.D = st.dev<const uint8_t>(o_desc) + (size_t)C * 32;
+  a.GS = e.d_gstart + (GRID_CELLS + 1);
+  a.GI = e.d_gitems + C;
+  a.best_idx = e.d_out;
+  a.best_dist = e.d_i32;
+  a.n_mp = n1;
+  launch_kf_project<KF_SIM3>(cd, a, 1, n1, s);
+  // KF2's points into KF1: vnMatch2 in d_out[K, K + n2), distances in d_i32 + K
+  if (n2 > 0) {
+    a.T0 = dS + 16;
+    a.T = dS + 48;
+    a.valid = st.dev<const uint8_t>(o_v2);
+    a.skip = st.dev<const uint8_t>(o_a2);
+    a.pos = st.dev<const float>(o_p2);
+    a.mind = st.dev<const float>(o_n2);
+    a.maxd = st.dev<const float>(o_x2);
+    a.mdesc = st.dev<const uint8_t>(o_d2);
+    a.K = dk;
+    a.D = st.dev<const uint8_t>(o_desc);
+    a.GS = e.d_gstart;
+    a.GI = e.d_gitems;
+    a.best_idx = e.d_out + K;
+    a.best_dist = e.d_i32 + K;
+    a.n_mp = n2;
+    launch_kf_project<KF_SIM3>(cd, a, 1, n2, s);
+  }
+  hipLaunchKernelGGL(k_sim3_agree, dim3(1), dim3(256), 0, s, n1, n2, e.d_out, e.d_out + K, e.d_i32b, e.d_out + 2 * K);
+  EAO_HIP_CHECK(hipGetLastError());
+  EAO_HIP_CHECK(e.res.reserve(sizeof(int) * ((size_t)n1 + 1)));
+  int* r = (int*)e.res.h;
+  EAO_HIP_CHECK(hipMemcpyAsync(r, e.d_i32b, sizeof(int) * n1, hipMemcpyDeviceToHost, s));
+  EAO_HIP_CHECK(hipMemcpyAsync(r + n1, e.d_out + 2 * K, sizeof(int), hipMemcpyDeviceToHost, s));
+  EAO_HIP_CHECK(hipStreamSynchronize(s));
+  std::memcpy(match12, r, sizeof(int) * n1);
+  return r[n1];
+}
+
+int eao_match_fuse_batch_device(eao_matcher* m, const eao_camera* cam, int nsearch, const float* d_Tcw, float th,
+                                int mp_cap, const int32_t* d_n_mp, const uint8_t* d_mp_valid,
+                                const float* d_mp_pos, const float* d_mp_normal, const float* d_mp_min_dist,
+                                const float* d_mp_max_dist, const uint8_t* d_mp_desc, float log_scale_factor,
+                                int cap, const int32_t* d_n_kf, const eao_keypoint* d_kf_kps,
+                                const uint8_t* d_kf_desc, int nlevels, const float* scale_factors,
+                                const float* inv_level_sigma2, int32_t* d_best_idx, int32_t* d_best_dist,
+                                int32_t* d_nfused, void* stream) {
+  int rc = batch_args(m, cam, nsearch, mp_cap, cap, nlevels, d_n_mp, d_n_kf, "eao_match_fuse_batch_device");
+  if (rc) return rc;
+  if (!d_Tcw || !d_mp_valid || !d_mp_pos || !d_mp_normal || !d_mp_min_dist || !d_mp_max_dist || !d_mp_desc ||
+      !d_kf_kps || !d_kf_desc || !scale_factors || !inv_level_sigma2 || !d_best_idx || !d_best_dist || !d_nfused) {
+    set_error("eao_match_fuse_batch_device: null buffer");
+    return EAO_E_ARG;
+  }
+  MatchEngine& e = m->e;
+  EAO_HIP_CHECK(hipSetDevice(e.dev));
+  hipStream_t s = stream ? (hipStream_t)stream : e.stream;
+  EAO_HIP_CHECK(hipMemcpyAsync(e.d_scales, scale_factors, sizeof(float) * nlevels, hipMemcpyHostToDevice, s));
+  EAO_HIP_CHECK(hipMemcpyAsync(e.d_scales + 32, inv_level_sigma2, sizeof(float) * nlevels, hipMemcpyHostToDevice, s));
+  EAO_HIP_CHECK(hipMemsetAsync(d_nfused, 0, sizeof(int) * nsearch, s));
+  const CamDev cd = make_cam(*cam);
+  const auto* CK = (const eao_keypoint_dev*)d_kf_kps;
+  rc = e.build_grid(cd, CK, d_n_kf, 0, cap, nsearch, s);
+  if (rc) return rc;
+  KfProj a{};
+  a.T = d_Tcw;
+  a.valid = d_mp_valid;
+  a.pos = d_mp_pos;
+  a.nrm = d_mp_normal;
+  a.mind = d_mp_min_dist;
+  a.maxd = d_mp_max_dist;
+  a.mdesc = d_mp_desc;
+  a.K = CK;
+  a.D = d_kf_desc;
+  a.GS = e.d_gstart;
+  a.GI = e.d_gitems;
+  a.scales = e.d_scales;
+  a.invsig2 = e.d_scales + 32;
+  a.best_idx = d_best_idx;
+  a.best_dist = d_best_dist;
+  a.nfound = d_nfused;
+  a.nq = d_n_mp;
+  a.qs = mp_cap;
+  a.cs = cap;
+  a.nlevels = nlevels;
+  a.th = th;
+  a.logsf = log_scale_factor;
+  launch_kf_project<KF_FUSE>(cd, a, nsearch, mp_cap, s);
+  EAO_HIP_CHECK(hipGetLastError());
+  return EAO_OK;
 }
 
 }  // extern "C"

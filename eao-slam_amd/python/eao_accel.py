@@ -331,6 +331,70 @@ class Matcher(_Handle):
             v(desc1), cap2, v(n2), v(kps2), v(desc2), v(prev), int(window), v(m12), v(nmatch),
             v(stream) if stream else None), "eao_match_init_batch_device")
 
+    # the keyframe matchers of the mapping and loop threads (monocular); mp = the map points'
+    # (valid, pos, normal, mind, maxd, desc)
+    def fuse(self, cam, Tcw, th, mp_valid, mp_pos, mp_normal, mp_mind, mp_maxd, mp_desc, logsf, kf_kps, kf_desc,
+             scales, inv_sigma2):
+        """ORBmatcher::Fuse(pKF, vpMapPoints, th) (ORBmatcher.cc:825-975) -> (nFused, best_idx, best_dist)."""
+        n = len(mp_valid)
+        bi, bd = np.full(n, -1, np.int32), np.full(n, 256, np.int32)
+        c = np.ascontiguousarray
+        a = [c(Tcw, np.float32), c(mp_valid, np.uint8), c(mp_pos, np.float32), c(mp_normal, np.float32),
+             c(mp_mind, np.float32), c(mp_maxd, np.float32), c(mp_desc, np.uint8), c(kf_kps), c(kf_desc, np.uint8),
+             c(scales, np.float32), c(inv_sigma2, np.float32)]  # kept alive over the call
+        nf = check(lib().eao_match_fuse(
+            self.h, ctypes.byref(cam), P(a[0]), ctypes.c_float(th), n, P(a[1]), P(a[2]), P(a[3]), P(a[4]), P(a[5]),
+            P(a[6]), ctypes.c_float(logsf), len(kf_kps), P(a[7]), P(a[8]), len(a[9]), P(a[9]), P(a[10]), P(bi),
+            P(bd)), "eao_match_fuse")
+        return nf, bi, bd
+
+    def fuse_sim3(self, cam, Scw, th, mp_valid, mp_pos, mp_normal, mp_mind, mp_maxd, mp_desc, logsf, kf_kps,
+                  kf_desc, scales):
+        """ORBmatcher::Fuse(pKF, Scw, vpPoints, th, vpReplacePoint) (ORBmatcher.cc:977-1100)."""
+        n = len(mp_valid)
+        bi, bd = np.full(n, -1, np.int32), np.full(n, 256, np.int32)
+        c = np.ascontiguousarray
+        a = [c(Scw, np.float32), c(mp_valid, np.uint8), c(mp_pos, np.float32), c(mp_normal, np.float32),
+             c(mp_mind, np.float32), c(mp_maxd, np.float32), c(mp_desc, np.uint8), c(kf_kps), c(kf_desc, np.uint8),
+             c(scales, np.float32)]  # kept alive over the call
+        nf = check(lib().eao_match_fuse_sim3(
+            self.h, ctypes.byref(cam), P(a[0]), ctypes.c_float(th), n, P(a[1]), P(a[2]), P(a[3]), P(a[4]), P(a[5]),
+            P(a[6]), ctypes.c_float(logsf), len(kf_kps), P(a[7]), P(a[8]), len(a[9]), P(a[9]), P(bi), P(bd)),
+            "eao_match_fuse_sim3")
+        return nf, bi, bd
+
+    def sim3(self, cam, Tcw1, Tcw2, s12, R12, t12, th, side1, side2, logsf, scales):
+        """ORBmatcher::SearchBySim3 (ORBmatcher.cc:1102-1326); side = (kps, desc, mp_valid, mp_pos, mp_mind,
+        mp_maxd, mp_desc, already_matched) -> (nFound, match12)."""
+        c = np.ascontiguousarray
+        sc = c(scales, np.float32)
+
+        def args(s):
+            kps, desc, valid, pos, mind, maxd, mdesc, already = s
+            keep = [c(kps), c(desc, np.uint8), c(valid, np.uint8), c(pos, np.float32), c(mind, np.float32),
+                    c(maxd, np.float32), c(mdesc, np.uint8), c(already, np.uint8)]
+            return keep, [len(kps)] + [P(a) for a in keep]
+        k1, a1 = args(side1)
+        k2, a2 = args(side2)
+        m12 = np.full(len(side1[0]), -1, np.int32)
+        g = [c(Tcw1, np.float32), c(Tcw2, np.float32), c(R12, np.float32), c(t12, np.float32)]
+        nf = check(lib().eao_match_sim3(
+            self.h, ctypes.byref(cam), P(g[0]), P(g[1]), ctypes.c_float(s12), P(g[2]), P(g[3]), ctypes.c_float(th),
+            *a1, *a2, ctypes.c_float(logsf), len(sc), P(sc), P(m12)), "eao_match_sim3")
+        return nf, m12
+
+    def fuse_batch_device(self, cam, nsearch, T, th, mp_cap, n_mp, valid, pos, normal, mind, maxd, desc, logsf, cap,
+                          n_kf, kf_kps, kf_desc, scales, inv_sigma2, best_idx, best_dist, nfused, stream=None):
+        """batched HBM-resident Fuse; the array arguments are device pointers (ints)."""
+        sc = np.ascontiguousarray(scales, np.float32)
+        isg = np.ascontiguousarray(inv_sigma2, np.float32)
+        v = ctypes.c_void_p
+        check(lib().eao_match_fuse_batch_device(
+            self.h, ctypes.byref(cam), nsearch, v(T), ctypes.c_float(th), mp_cap, v(n_mp), v(valid), v(pos),
+            v(normal), v(mind), v(maxd), v(desc), ctypes.c_float(logsf), cap, v(n_kf), v(kf_kps), v(kf_desc), len(sc),
+            P(sc), P(isg), v(best_idx), v(best_dist), v(nfused), v(stream) if stream else None),
+            "eao_match_fuse_batch_device")
+
 
 class Pose(_Handle):
     """Optimizer::PoseOptimization replacement (reference src/Optimizer.cc:243-457), monocular edges."""
@@ -429,6 +493,34 @@ class Vocab(_Handle):
                                                       v(d_n1), *[v(x) for x in kf1], *[v(x) for x in kf2], v(d_match),
                                                       v(d_nm), v(stream) if stream else None),
               "eao_search_by_bow_kf_batch_device")
+
+    def search_triangulation(self, cam2, F12, Ow1, Tcw2, check_ori, kps1, desc1, has_mp1, fv1, kps2, desc2, has_mp2,
+                             fv2, scales, level_sigma2):
+        """SearchForTriangulation (ORBmatcher.cc:657-823): fv = (node_ids, node_start, node_feats)
+        -> (nmatches, match12); vMatchedPairs = [(i, match12[i]) for i where match12[i] >= 0]."""
+        m = np.full(len(kps1), -1, np.int32)
+        c = np.ascontiguousarray
+        a = [c(x, np.int32) for x in fv1]
+        b = [c(x, np.int32) for x in fv2]
+        g = [c(F12, np.float32), c(Ow1, np.float32), c(Tcw2, np.float32), c(kps1), c(desc1, np.uint8),
+             c(has_mp1, np.uint8), c(kps2), c(desc2, np.uint8), c(has_mp2, np.uint8), c(scales, np.float32),
+             c(level_sigma2, np.float32)]  # kept alive over the call
+        n = check(lib().eao_search_for_triangulation(
+            self.h, ctypes.byref(cam2), P(g[0]), P(g[1]), P(g[2]), int(check_ori), len(kps1), P(g[3]), P(g[4]),
+            P(g[5]), len(a[0]), P(a[0]), P(a[1]), P(a[2]), len(kps2), P(g[6]), P(g[7]), P(g[8]), len(b[0]), P(b[0]),
+            P(b[1]), P(b[2]), len(g[9]), P(g[9]), P(g[10]), P(m)), "eao_search_for_triangulation")
+        return n, m
+
+    def search_triangulation_batch_device(self, cam2, check_ori, nsearch, cap, d_F12, d_Ow1, d_Tcw2, d_n1, kf1, kf2,
+                                          scales, level_sigma2, d_match, d_nm, stream=None):
+        """kf1 / kf2: (kps, desc, has_mp, nn, node_ids, node_start, node_feats) device pointers."""
+        v = ctypes.c_void_p
+        sc = np.ascontiguousarray(scales, np.float32)
+        sg = np.ascontiguousarray(level_sigma2, np.float32)
+        check(lib().eao_search_for_triangulation_batch_device(
+            self.h, ctypes.byref(cam2), int(check_ori), nsearch, cap, v(d_F12), v(d_Ow1), v(d_Tcw2), v(d_n1),
+            *[v(x) for x in kf1], *[v(x) for x in kf2], len(sc), P(sc), P(sg), v(d_match), v(d_nm),
+            v(stream) if stream else None), "eao_search_for_triangulation_batch_device")
 
     def transform_batch_device(self, nframes, cap, d_counts, d_desc, levelsup, d_wid, d_ww, d_nw, d_nid, d_ns, d_nf,
                                d_nn, stream=None):

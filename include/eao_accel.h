@@ -222,6 +222,84 @@ int eao_match_init_batch_device(eao_matcher* m, const eao_camera* cam, int nsear
                                 float* d_prev_matched_xy, int window, int32_t* d_matches12, int32_t* d_nmatches,
                                 void* stream);
 
+/* --- the keyframe matchers of the mapping and loop threads. Monocular (mvuRight < 0 everywhere), like
+   every configuration here: the stereo branch of Fuse (src/ORBmatcher.cc:914-927) is not built. Each
+   projects map points into a keyframe and searches KeyFrame::GetFeaturesInArea (src/KeyFrame.cc:612-651;
+   64x48 grid, cells walked ix outer / iy inner, keypoints of a cell in index order, |dx| < r && |dy| < r,
+   no level filter), keeps keypoints of octave [level-1, level] around the clamped PredictScale level
+    and takes the smallest Hamming distance, on ties the FIRST keypoint in that walk order.
+   The engine returns indices and distances; the side effects (Replace, AddObservation, AddMapPoint,
+   vpReplacePoint) stay with the caller, who applies the results in index order. The points of a call are
+   searched in parallel on the flags as they were at the call (see DESIGN.md section 2 for why that is the
+   reference's result). Keypoint octaves lie in [0, nlevels). */
+
+/* ORBmatcher::Fuse(pKF, vpMapPoints, th) (src/ORBmatcher.cc:825-975), called by
+   LocalMapping::SearchInNeighbors (src/LocalMapping.cc:494,519).
+   mp_valid[i] = vpMapPoints[i] && !isBad() && !IsInKeyFrame(pKF); mp_pos / mp_normal / mp_min_dist /
+   mp_max_dist / mp_desc = GetWorldPos() / GetNormal() / mfMinDistance / mfMaxDistance / GetDescriptor()
+   of that point; kf_kps = pKF->mvKeysUn, kf_desc = pKF->mDescriptors; Tcw = pKF's pose (Ow is computed
+   from it); log_scale_factor, scale_factors, inv_level_sigma2 = pKF's mfLogScaleFactor, mvScaleFactors,
+   mvInvLevelSigma2. Gates in the reference's order: z < 0, IsInImage, distance in [0.8 min, 1.2 max],
+   PO.Pn < 0.5 dist3D, then per keypoint the octave and e2 * inv_level_sigma2 > 5.99.
+   best_dist[i] = the smallest distance among the keypoints that passed (256: none passed, or the point
+   was gated out); best_idx[i] = that keypoint when best_dist[i] <= TH_LOW (50), else -1. The caller
+   fuses point i into pKF->GetMapPoint(best_idx[i]) (Replace, with the isBad() re-check) or adds the
+   observation. Returns the number of points with best_idx >= 0 (nFused) or an EAO_E_* error. */
+int eao_match_fuse(eao_matcher* m, const eao_camera* cam, const float* Tcw, float th, int n_mp,
+                   const uint8_t* mp_valid, const float* mp_pos, const float* mp_normal,
+                   const float* mp_min_dist, const float* mp_max_dist, const uint8_t* mp_desc,
+                   float log_scale_factor, int n_kf, const eao_keypoint* kf_kps, const uint8_t* kf_desc,
+                   int nlevels, const float* scale_factors, const float* inv_level_sigma2, int32_t* best_idx,
+                   int32_t* best_dist);
+
+/* ORBmatcher::Fuse(pKF, Scw, vpPoints, th, vpReplacePoint) (src/ORBmatcher.cc:977-1100), called by
+   LoopClosing::SearchAndFuse (src/LoopClosing.cc:596). Scw [4][4] is decomposed inside (scw = |row 0|,
+   Rcw = sRcw / scw, tcw = t / scw, Ow = -Rcw^T tcw). mp_valid[i] = !vpPoints[i]->isBad() &&
+   !spAlreadyFound.count(vpPoints[i]) (spAlreadyFound = pKF->GetMapPoints()). The gates of eao_match_fuse
+   without the chi-square one; outputs and return value as there. vpReplacePoint[i] =
+   pKF->GetMapPoint(best_idx[i]) when that is set and not bad; otherwise the caller adds the observation. */
+int eao_match_fuse_sim3(eao_matcher* m, const eao_camera* cam, const float* Scw, float th, int n_mp,
+                        const uint8_t* mp_valid, const float* mp_pos, const float* mp_normal,
+                        const float* mp_min_dist, const float* mp_max_dist, const uint8_t* mp_desc,
+                        float log_scale_factor, int n_kf, const eao_keypoint* kf_kps, const uint8_t* kf_desc,
+                        int nlevels, const float* scale_factors, int32_t* best_idx, int32_t* best_dist);
+
+/* ORBmatcher::SearchBySim3(pKF1, pKF2, vpMatches12, s12, R12, t12, th) (src/ORBmatcher.cc:1102-1326),
+   called by LoopClosing::ComputeSim3 (src/LoopClosing.cc:323). Tcw1 / Tcw2 = the keyframes' poses,
+   R12 [3][3] row-major, t12 [3]. Per side k: kps = mvKeysUn, desc = mDescriptors, mp_valid[i] =
+   GetMapPointMatches()[i] && !isBad() with that point's position / distances / descriptor, and
+   already_matched = vbAlreadyMatched1 / 2 as the reference fills them from vpMatches12 (:1132-1142):
+   already_matched1[i] = vpMatches12[i] != NULL, already_matched2[vpMatches12[i]->GetIndexInKeyFrame(pKF2)]
+   = 1. KF1's points are searched in KF2 through sR21, t21 and KF2's in KF1 through sR12, t12 (z < 0,
+   IsInImage, the distance range on the norm of the camera-frame point; no viewing-angle gate; a best
+   distance <= TH_HIGH (100) is accepted), then match12[i1] = the KF2 feature i2 with vnMatch1[i1] == i2
+   and vnMatch2[i2] == i1, else -1: the caller sets vpMatches12[i1] = KF2's map point i2. Returns nFound
+   or an EAO_E_* error. */
+int eao_match_sim3(eao_matcher* m, const eao_camera* cam, const float* Tcw1, const float* Tcw2, float s12,
+                   const float* R12, const float* t12, float th, int n1, const eao_keypoint* kps1,
+                   const uint8_t* desc1, const uint8_t* mp_valid1, const float* mp_pos1,
+                   const float* mp_min_dist1, const float* mp_max_dist1, const uint8_t* mp_desc1,
+                   const uint8_t* already_matched1, int n2, const eao_keypoint* kps2, const uint8_t* desc2,
+                   const uint8_t* mp_valid2, const float* mp_pos2, const float* mp_min_dist2,
+                   const float* mp_max_dist2, const uint8_t* mp_desc2, const uint8_t* already_matched2,
+                   float log_scale_factor, int nlevels, const float* scale_factors, int32_t* match12);
+
+/* batched, HBM-resident eao_match_fuse: the form LocalMapping::SearchInNeighbors queues (one set of
+   points into every neighbour, every neighbour's points into the current keyframe). Search s reads point
+   slot s ([nsearch][mp_cap] arrays, count d_n_mp[s]) and keyframe slot s ([nsearch][cap] keypoints /
+   descriptors, count d_n_kf[s], pose d_Tcw[s][16]); writes d_best_idx / d_best_dist [nsearch][mp_cap] for
+   the first d_n_mp[s] points of each slot (entries past the count are left untouched) and d_nfused[s].
+   scale_factors / inv_level_sigma2 are host arrays. nsearch <= max_batch, mp_cap and cap <= max_kps.
+   Asynchronous on `stream` (NULL: the matcher's own stream). */
+int eao_match_fuse_batch_device(eao_matcher* m, const eao_camera* cam, int nsearch, const float* d_Tcw, float th,
+                                int mp_cap, const int32_t* d_n_mp, const uint8_t* d_mp_valid,
+                                const float* d_mp_pos, const float* d_mp_normal, const float* d_mp_min_dist,
+                                const float* d_mp_max_dist, const uint8_t* d_mp_desc, float log_scale_factor,
+                                int cap, const int32_t* d_n_kf, const eao_keypoint* d_kf_kps,
+                                const uint8_t* d_kf_desc, int nlevels, const float* scale_factors,
+                                const float* inv_level_sigma2, int32_t* d_best_idx, int32_t* d_best_dist,
+                                int32_t* d_nfused, void* stream);
+
 /* --- per-frame line detection: replaces line_lbd_detect::detect_raw_lines +
    filter_lines (src/Frame.cc:324-328; src/line_detect/line_lbd_allclass.cpp:137-214)
    with the tracker's single octave (Tracking.cc:161-163): GaussianBlur(5x5, sigma 1),
@@ -553,6 +631,44 @@ int eao_search_by_bow_kf_batch_device(eao_vocab* v, float nnratio, int check_ori
                                       const int32_t* d_nn2, const int32_t* d_node_ids2,
                                       const int32_t* d_node_start2, const int32_t* d_node_feats2,
                                       int32_t* d_match12, int32_t* d_nmatches, void* stream);
+
+/* ORBmatcher::SearchForTriangulation(pKF1, pKF2, F12, vMatchedPairs, bOnlyStereo = false)
+   (src/ORBmatcher.cc:657-823, with CheckDistEpipolarLine :140-157), called by
+   LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:273). Monocular: the bOnlyStereo path is not built.
+   cam2 = pKF2's intrinsics, F12 [3][3] row-major (ComputeF12 stays with the caller), Ow1 =
+   pKF1->GetCameraCenter(), Tcw2 = pKF2's pose (the epipole C2 = R2w * Ow1 + t2w is computed inside).
+   Per side: kps = mvKeysUn, desc = mDescriptors, has_mp[i] = GetMapPoint(i) != NULL (such features are
+   skipped on both sides) and the FeatureVector as eao_bow_transform returns it. scale_factors /
+   level_sigma2 = pKF2's mvScaleFactors / mvLevelSigma2. For every KF1 feature without a map point the
+   KF2 features of the same vocabulary node are scanned in list order; one is skipped when it has a map
+   point, when dist > TH_LOW (50) or dist > bestDist (an equal distance replaces: the LAST candidate wins
+   ties), when it lies within 100 * scale_factors[octave] (squared pixels) of the epipole, or when it fails
+   CheckDistEpipolarLine. The reference never sets vbMatched2: a KF2 feature may be matched more than
+   once. check_ori applies the rotation histogram over idx1. match12[i1] = the KF2 feature (-1: none);
+   vMatchedPairs = {(i, match12[i]) : match12[i] >= 0} in ascending i. Returns nmatches (>= 0) or an
+   EAO_E_* error (EAO_E_CAPACITY: a vocabulary node holds more than 1024 KF2 features). */
+int eao_search_for_triangulation(eao_vocab* v, const eao_camera* cam2, const float* F12, const float* Ow1,
+                                 const float* Tcw2, int check_ori, int n1, const eao_keypoint* kps1,
+                                 const uint8_t* desc1, const uint8_t* has_mp1, int nn1, const int32_t* node_ids1,
+                                 const int32_t* node_start1, const int32_t* node_feats1, int n2,
+                                 const eao_keypoint* kps2, const uint8_t* desc2, const uint8_t* has_mp2, int nn2,
+                                 const int32_t* node_ids2, const int32_t* node_start2, const int32_t* node_feats2,
+                                 int nlevels, const float* scale_factors, const float* level_sigma2,
+                                 int32_t* match12);
+/* batched, HBM-resident: search s pairs KF1 slot s with KF2 slot s (arrays as
+   eao_search_by_bow_kf_batch_device, has_mp flags in place of the valid flags) with d_F12[s][9],
+   d_Ow1[s][3], d_Tcw2[s][16]; scale_factors / level_sigma2 are host arrays. Writes d_match12
+   [nsearch][cap] (-1 where unmatched, the whole slot) and d_nmatches [nsearch] (EAO_E_CAPACITY for a
+   search in which a vocabulary node holds more than 1024 KF2 features). nsearch <= max_batch, cap <=
+   max_kps; the FeatureVector preconditions of eao_search_by_bow_batch_device. */
+int eao_search_for_triangulation_batch_device(
+    eao_vocab* v, const eao_camera* cam2, int check_ori, int nsearch, int cap, const float* d_F12,
+    const float* d_Ow1, const float* d_Tcw2, const int32_t* d_n1, const eao_keypoint* d_kps1,
+    const uint8_t* d_desc1, const uint8_t* d_has_mp1, const int32_t* d_nn1, const int32_t* d_node_ids1,
+    const int32_t* d_node_start1, const int32_t* d_node_feats1, const eao_keypoint* d_kps2,
+    const uint8_t* d_desc2, const uint8_t* d_has_mp2, const int32_t* d_nn2, const int32_t* d_node_ids2,
+    const int32_t* d_node_start2, const int32_t* d_node_feats2, int nlevels, const float* scale_factors,
+    const float* level_sigma2, int32_t* d_match12, int32_t* d_nmatches, void* stream);
 
 #ifdef __cplusplus
 }

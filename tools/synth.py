@@ -792,3 +792,240 @@ def bow_pair(voc, n_kf=1000, n_f=1000, seed=0, overlap=0.7, valid=0.8):
     fk["angle"][dst] = np.mod(kk["angle"][src] - rot + rng.normal(0, 4, m), 360).astype(np.float32)
     kv = (rng.random(n_kf) < valid).astype(np.uint8)
     return kk, kd, kv, fk, fd
+
+
+# ---- scenes for the keyframe matchers (SearchForTriangulation, Fuse, SearchBySim3): checked by
+# tools/kfmatch_ref.py, used by tests/test_kfmatch_ref.py (CPU) and tests/test_gpu_kfmatch.py
+_KP_DT = [("x", "f4"), ("y", "f4"), ("size", "f4"), ("angle", "f4"), ("response", "f4"), ("octave", "i4"),
+          ("class_id", "i4")]
+
+
+def level_tables(nlevels=8, scale=1.2):
+    """mvScaleFactors, mvLevelSigma2, mvInvLevelSigma2 and mfLogScaleFactor as ORBextractor fills them
+    (float32: running product, square, reciprocal; ORBextractor.cc:422-440)."""
+    sf = np.ones(nlevels, np.float32)
+    for i in range(1, nlevels):
+        sf[i] = np.float32(sf[i - 1] * np.float32(scale))
+    sig = (sf * sf).astype(np.float32)
+    inv = (np.float32(1.0) / sig).astype(np.float32)
+    return sf, sig, inv, np.float32(np.log(np.float32(scale)))
+
+
+def two_keyframes(seed=0, n_pts=850, n_clutter=120, forward=False, voc=None, K=TUM3_K, w=640, h=480, nlevels=8,
+                  scale=1.2, n_dup=24, n_baseline=0, kp_flips=5):
+    """Two keyframes with a known relative pose observing the same world points. -> dict with
+    T1 / T2 (Tcw, float32), P [n][3] world points (float64), base [n][32] descriptors (around
+    vocabulary leaves when voc is given), and per view k = 1, 2: kps<k>, desc<k>, pt<k> (the world
+    point of each keypoint, -1 for clutter and planted duplicates' twin = the same point).
+    forward: camera 1 stands in front of camera 2, so the epipole lies inside image 2; n_baseline
+    world points are planted next to the line through the two centres (they project next to the
+    epipole). n_dup keypoints of view 2 get a twin: the same descriptor, octave and angle, less than
+    a pixel away (equal Hamming distances)."""
+    rng = np.random.default_rng(seed)
+    fx, fy, cx, cy = K
+    tgt = np.array([0.0, 0.0, 0.0])
+    if forward:
+        e2 = np.array([0.15, -4.2, 0.1])
+        e1 = e2 + 0.22 * (tgt - e2) + np.array([0.03, 0.0, 0.02])
+    else:
+        e1, e2 = np.array([-0.4, -3.6, 0.3]), np.array([0.45, -3.4, 0.1])
+    T1, T2 = _look_at(e1, tgt).astype(np.float64), _look_at(e2, tgt).astype(np.float64)
+    T2[:3, :3] = rodrigues(rng.normal(0, 0.03, 3)) @ T2[:3, :3]
+    T2[:3, 3] = -T2[:3, :3] @ e2
+    P = rng.uniform([-1.7, -1.0, -1.3], [1.7, 1.6, 1.3], (n_pts, 3))
+    if n_baseline:
+        d = (e1 - e2) / np.linalg.norm(e1 - e2)
+        P[:n_baseline] = e1 + d * rng.uniform(1.0, 4.0, (n_baseline, 1)) + rng.normal(0, 0.012, (n_baseline, 3))
+    n = len(P)
+    base = bow_features(voc, n, seed + 31, flips=3) if voc is not None else rng.integers(0, 256, (n, 32), dtype=np.uint8)
+    oct1 = rng.integers(0, nlevels, n)
+    ang1 = rng.uniform(0, 360, n)
+    rot = rng.uniform(20, 340)
+    out = {"T1": T1.astype(np.float32), "T2": T2.astype(np.float32), "P": P, "base": base, "e1": e1, "e2": e2,
+           "oct1": oct1}
+    for k, T in ((1, T1), (2, T2)):
+        Xc = P @ T[:3, :3].T + T[:3, 3]
+        u = fx * Xc[:, 0] / Xc[:, 2] + cx
+        v = fy * Xc[:, 1] / Xc[:, 2] + cy
+        octv = oct1 if k == 1 else np.clip(oct1 + rng.choice([-1, 0, 0, 0, 0, 1], n), 0, nlevels - 1)
+        sc = scale ** octv.astype(np.float64)
+        u = u + rng.normal(0, 0.5, n) * sc
+        v = v + rng.normal(0, 0.5, n) * sc
+        vis = np.nonzero((Xc[:, 2] > 0.2) & (u >= 1) & (u < w - 1) & (v >= 1) & (v < h - 1))[0]
+        ang = ang1 if k == 1 else np.mod(ang1 - rot + rng.normal(0, 4, n), 360)
+        m = len(vis)
+        dup = vis[rng.permutation(m)[:n_dup]] if k == 2 else np.zeros(0, np.int64)
+        tot = m + len(dup) + n_clutter
+        kps = np.zeros(tot, _KP_DT)
+        desc = np.zeros((tot, 32), np.uint8)
+        pt = np.full(tot, -1, np.int32)
+        kps["x"][:m], kps["y"][:m], kps["octave"][:m], kps["angle"][:m] = u[vis], v[vis], octv[vis], ang[vis]
+        desc[:m] = _flip_bits(base[vis].copy(), kp_flips, rng)
+        pt[:m] = vis
+        kps["x"][m + len(dup):] = rng.uniform(0, w, n_clutter)
+        kps["y"][m + len(dup):] = rng.uniform(0, h, n_clutter)
+        kps["octave"][m + len(dup):] = rng.integers(0, nlevels, n_clutter)
+        kps["angle"][m + len(dup):] = rng.uniform(0, 360, n_clutter)
+        desc[m + len(dup):] = (bow_features(voc, n_clutter, seed + 77 + k) if voc is not None
+                               else rng.integers(0, 256, (n_clutter, 32), dtype=np.uint8))
+        order = rng.permutation(tot)
+        if len(dup):  # twins: placed after the shuffle so the copy is exact
+            where = {int(p): i for i, p in enumerate(pt[:m])}
+            for j, p in enumerate(dup):
+                s = where[int(p)]
+                kps[m + j] = kps[s]
+                kps["x"][m + j] += 0.6
+                kps["y"][m + j] += 0.3
+                desc[m + j] = desc[s]
+                pt[m + j] = p
+        kps["size"], kps["class_id"] = 31 * scale ** kps["octave"].astype(np.float64), -1
+        out["kps%d" % k], out["desc%d" % k], out["pt%d" % k] = kps[order], desc[order], pt[order]
+    return out
+
+
+def fundamental_12(T1, T2, K=TUM3_K):
+    """F12 of LocalMapping::ComputeF12 (src/LocalMapping.cc:704-720) from the two poses, formed in
+    float64 and cast: F12 = K1^-T [t12]x R12 K2^-1, R12 = R1w R2w^T, t12 = -R12 t2w + t1w."""
+    T1, T2 = np.asarray(T1, np.float64), np.asarray(T2, np.float64)
+    R12 = T1[:3, :3] @ T2[:3, :3].T
+    t12 = -R12 @ T2[:3, 3] + T1[:3, 3]
+    tx = np.array([[0, -t12[2], t12[1]], [t12[2], 0, -t12[0]], [-t12[1], t12[0], 0]])
+    Km = np.array([[K[0], 0, K[2]], [0, K[1], K[3]], [0, 0, 1.0]])
+    Ki = np.linalg.inv(Km)
+    return (Ki.T @ tx @ R12 @ Ki).astype(np.float32)
+
+
+def camera_center(T):
+    T = np.asarray(T, np.float64)
+    return (-T[:3, :3].T @ T[:3, 3]).astype(np.float32)
+
+
+def map_points_of(sc, view, idx, seed=0, nlevels=8, scale=1.2, flips=4, spoil=14):
+    """Map points for the world points idx of a two_keyframes scene, as observed from keyframe `view`
+    (its centre gives the normal, its distance and octave the scale-invariance range:
+    mfMaxDistance = dist * scale^octave, here half a level lower so PredictScale does not sit on an
+    integer; mfMinDistance = mfMaxDistance / scale^(nlevels-1)). The first 6 * spoil points are
+    spoiled, `spoil` each, to trip one gate when projected into the OTHER keyframe: behind the
+    camera, outside the image, out of the distance range, seen from behind (normal flipped),
+    2.8 level-sigma off in u (chi-square), and a distance range far too large (predicted level above
+    nlevels - 1, clamped). -> dict(valid, pos, normal, mind, maxd, desc, cls)."""
+    rng = np.random.default_rng(seed)
+    idx = np.asarray(idx)
+    n = len(idx)
+    own = sc["e%d" % view]
+    To = np.asarray(sc["T%d" % (3 - view)], np.float64)
+    eo = sc["e%d" % (3 - view)]
+    Rwc = To[:3, :3].T
+    P = sc["P"][idx].copy()
+    d = np.linalg.norm(P - own, axis=1)
+    nrm = (P - own) / d[:, None]
+    octv = sc["oct1"][idx].astype(np.float64)
+    maxd = d * scale ** (octv - 0.5)
+    mind = maxd / scale ** (nlevels - 1)
+    cls = np.zeros(n, np.int32)
+    for c in range(6):
+        cls[c * spoil:(c + 1) * spoil] = c + 1
+    cls = cls[:n]
+    b = cls == 1
+    P[b] = eo - (P[b] - eo)
+    b = cls == 2
+    P[b] = P[b] + (Rwc @ np.array([6.0, 0.0, 0.0]))
+    maxd[cls == 3] = 0.5 * d[cls == 3]
+    nrm[cls == 4] *= -1
+    b = np.nonzero(cls == 5)[0]
+    zc = (P[b] @ To[:3, :3].T + To[:3, 3])[:, 2]
+    P[b] = P[b] + (2.8 * scale ** octv[b] * zc / TUM3_K[0])[:, None] * Rwc[:, 0]
+    maxd[cls == 6] *= scale ** 12
+    desc = _flip_bits(sc["base"][idx].copy(), flips, rng)
+    valid = (rng.random(n) < 0.93).astype(np.uint8)
+    valid[:6 * spoil] = 1
+    return {"valid": valid, "pos": P.astype(np.float32), "normal": nrm.astype(np.float32),
+            "mind": mind.astype(np.float32), "maxd": maxd.astype(np.float32), "desc": desc, "cls": cls}
+
+
+def sim3_perturb(T1, T2, seed=0, scale=1.03, rot_err=0.004, t_err=0.01):
+    """(s12, R12 [3][3], t12 [3]) float32: the true relative pose of two keyframes (camera-2
+    coordinates into camera 1, p1 = s12 R12 p2 + t12) with a scale factor, a small rotation and a
+    translation error applied -- what Sim3Solver hands SearchBySim3."""
+    rng = np.random.default_rng(seed)
+    T1, T2 = np.asarray(T1, np.float64), np.asarray(T2, np.float64)
+    R12 = T1[:3, :3] @ T2[:3, :3].T
+    t12 = T1[:3, 3] - R12 @ T2[:3, 3]
+    R12 = rodrigues(rng.normal(0, rot_err, 3)) @ R12
+    t12 = t12 + rng.normal(0, t_err, 3)
+    return np.float32(scale), R12.astype(np.float32), t12.astype(np.float32)
+
+
+def fuse_scene(seed=0, n_mp=600, n_kf=1000):
+    """The Fuse input of the tests: map points seen from keyframe 1 projected into keyframe 2 (its
+    first n_kf keypoints). -> dict(T, mp (map_points_of), kps, desc)."""
+    sc = two_keyframes(seed, n_clutter=220)
+    seen = np.unique(sc["pt2"][sc["pt2"] >= 0])
+    rng = np.random.default_rng(seed + 5)
+    idx = rng.permutation(seen)[:n_mp]
+    mp = map_points_of(sc, 1, idx, seed + 6)
+    kps, desc = sc["kps2"], sc["desc2"]
+    if n_kf is not None:
+        kps, desc = kps[:n_kf], desc[:n_kf]
+    return {"T": sc["T2"], "mp": mp, "kps": kps, "desc": desc}
+
+
+def sim3_scene(seed=0, n1=None, n2=None, scale=1.004):
+    """The SearchBySim3 input of the tests: every keypoint of the two keyframes that observes a world
+    point holds a map point (some spoiled, map_points_of); some pairs are already matched, and 20
+    matched features of keyframe 2 hold no valid point (their partners fail the agreement check).
+    -> dict(T1, T2, s12, R12, t12, side1, side2), side = dict(kps, desc, valid, pos, mind, maxd,
+    mp_desc, already)."""
+    sc = two_keyframes(seed + 100)
+    rng = np.random.default_rng(seed + 9)
+    sides = []
+    for k, n in ((1, n1), (2, n2)):
+        pt = sc["pt%d" % k]
+        mp = map_points_of(sc, k, np.where(pt >= 0, pt, 0), seed + 10 + k)
+        valid = (mp["valid"] & (pt >= 0)).astype(np.uint8)
+        s = {"kps": sc["kps%d" % k], "desc": sc["desc%d" % k], "valid": valid, "pos": mp["pos"], "mind": mp["mind"],
+             "maxd": mp["maxd"], "mp_desc": mp["desc"], "already": np.zeros(len(pt), np.uint8), "pt": pt}
+        sides.append(s)
+    s1, s2 = sides
+    first2 = {}
+    for j, p in enumerate(s2["pt"]):
+        if p >= 0:
+            first2.setdefault(int(p), j)
+    both = [i for i, p in enumerate(s1["pt"]) if int(p) in first2 and s1["valid"][i]]
+    pick = rng.permutation(both)
+    for i in pick[:60]:  # vpMatches12 already set: both sides skip the pair
+        s1["already"][i] = 1
+        s2["already"][first2[int(s1["pt"][i])]] = 1
+    for i in pick[60:80]:
+        s2["valid"][first2[int(s1["pt"][i])]] = 0
+    if n1 is not None:
+        s1 = {k: v[:n1] for k, v in s1.items()}
+    if n2 is not None:
+        s2 = {k: v[:n2] for k, v in s2.items()}
+    s12, R12, t12 = sim3_perturb(sc["T1"], sc["T2"], seed + 3, scale=scale)
+    return {"T1": sc["T1"], "T2": sc["T2"], "s12": s12, "R12": R12, "t12": t12, "side1": s1, "side2": s2}
+
+
+def triangulation_scene(voc, seed=0, n_pts=850, n_clutter=120):
+    """The SearchForTriangulation input of the tests: camera 1 in front of camera 2 (the epipole
+    inside image 2, 40 world points planted next to it), descriptors around vocabulary leaves, some
+    features already holding map points, 30 clutter keypoints of keyframe 2 carrying the descriptor
+    of a true one (right descriptor, wrong place) and 25 true matches with a random angle.
+    -> dict(F12, Ow1, T2, kps1, desc1, has1, kps2, desc2, has2); the FeatureVectors are the
+    caller's (eao_bow_transform / the oracle's bow_transform on desc1, desc2)."""
+    sc = two_keyframes(seed + 200, n_pts=n_pts, n_clutter=n_clutter, forward=True, voc=voc, n_baseline=40,
+                       kp_flips=2, n_dup=40)
+    rng = np.random.default_rng(seed + 13)
+    k1, d1, p1 = sc["kps1"], sc["desc1"], sc["pt1"]
+    k2, d2, p2 = sc["kps2"].copy(), sc["desc2"].copy(), sc["pt2"]
+    has1 = ((rng.random(len(k1)) < 0.35) & (p1 >= 40)).astype(np.uint8)
+    has2 = ((rng.random(len(k2)) < 0.35) & (p2 >= 40)).astype(np.uint8)
+    true2 = np.nonzero((p2 >= 40) & (has2 == 0))[0]
+    clutter2 = np.nonzero(p2 < 0)[0]
+    src = rng.permutation(true2)
+    for c, s in zip(clutter2[:30], src[:30]):
+        d2[c] = d2[s]
+        k2["octave"][c] = k2["octave"][s]
+    k2["angle"][src[30:55]] = rng.uniform(0, 360, 25)
+    return {"F12": fundamental_12(sc["T1"], sc["T2"]), "Ow1": camera_center(sc["T1"]), "T2": sc["T2"], "kps1": k1,
+            "desc1": d1, "has1": has1, "kps2": k2, "desc2": d2, "has2": has2}
